@@ -15,6 +15,10 @@ gradient reduction overlapped with backward, fused momentum-SGD update.
 Timing: W untimed warmup steps, then barrier + device sync, K timed steps,
 barrier + device sync; the elapsed time is the MAX over ranks; rank 0 prints
 one JSON line.  ``value`` = N * per_gpu_batch * K / elapsed (weak scaling).
+
+A plain run does only that.  ``--full`` adds the measurements that take runs of their own (the BERT-base
+line under ``extra.bert_base``); ``--dump-outputs DIR`` writes the variables the last timed step left behind
+as ``DIR/*.npy`` (same arguments, same inputs: two builds can be compared output for output).
 """
 import argparse
 import json
@@ -28,6 +32,10 @@ import time
 # (profiles/rocprof_resnet50_stock_torch_ops_r1.md).  vs_baseline divides by that rate x N
 # (ideal linear scaling of the comparator, i.e. a conservative ratio for N > 1).
 BASELINE_IMAGES_PER_SEC_PER_GPU = 5966.38
+
+# --dump-outputs: elements kept of a large variable (ResNet-50: 3.06 M of 25.6 M weights, 12 MB in all)
+DUMP_SAMPLE = 65536
+DUMP_SEED = 20240229
 
 
 def parse():
@@ -49,9 +57,18 @@ def parse():
     p.add_argument("--ref_rate", type=float, default=None,
                    help="per-GPU images/sec of the N=1 run of this config, for scaling_efficiency (default: the rate the "
                         "last N=1 run of the same config cached in .bench_n1_rate.json)")
+    p.add_argument("--full", action="store_true",
+                   help="also take the measurements that need runs of their own (today: BERT-base, see --bert); a "
+                        "plain run only sets up, warms up, times --steps steps and prints the result line")
     p.add_argument("--bert", type=int, default=-1,
-                   help="also measure BERT-base (bench/bert_bench.py, a child process run before the ResNet job) and "
-                        "attach it under extra.bert_base; -1: on for the default 1-GPU run")
+                   help="with --full: also measure BERT-base (bench/bert_bench.py, a child process run before the "
+                        "ResNet job) and attach it under extra.bert_base; -1: on for the default 1-GPU run, 0: off")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last step left a caller as DIR/<name>.npy (float32): "
+                        "the variables after the update (weights.npy: every trainable variable in creation order, "
+                        "whole if it has at most %d elements, else a fixed seeded sample of that many; "
+                        "moving_stats.npy: every other variable, whole), global_step.npy, and loss.npy (forward "
+                        "of the same batch on those variables)" % DUMP_SAMPLE)
     return p.parse_args()
 
 
@@ -61,7 +78,7 @@ def _bert_child(args):
     import subprocess
     want = args.bert if args.bert >= 0 else int(args.gpus == 1 and args.image_size == 224
                                                    and "RANK" not in os.environ)
-    if not want:
+    if not (args.full and want):
         return None
     here = os.path.dirname(os.path.abspath(__file__))
     cmd = [sys.executable, os.path.join(here, "bench", "bert_bench.py"), "--steps", "20", "--warmup", "5"]
@@ -73,6 +90,45 @@ def _bert_child(args):
                                         "baseline", "config") if k in rec}
     except Exception as e:  # noqa: BLE001 - the ResNet measurement must not depend on it
         return {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
+
+
+def _dump_outputs(out_dir, sess, loss, rank):
+    """--dump-outputs: a training step returns nothing; what it leaves a caller are the updated variables.
+    Collective in sharded mode (the fp32 masters are all-gathered); rank 0 writes.  The sample indices depend
+    only on DUMP_SEED and the variables' sizes, so two builds write the same elements."""
+    import numpy as np
+    import torch
+    from mdtf.train import variables as V
+    from mdtf.train import step as S
+    for op in S.train_ops():
+        if op.reducer is not None:
+            op.reducer.gather_full_master()
+    loss_value = float(sess.run(loss))
+    if rank != 0:
+        return
+    store = V.get_store()
+    trainable = store.trainable_variables()
+    others = [v for v in store.global_variables() if not v.trainable]
+    budget = (48 << 20) // 4                                        # elements; the whole dump stays under 64 MB
+    other_elems = sum(v.numel() for v in others)
+    keep = max(1, min(DUMP_SAMPLE, (budget - min(other_elems, budget // 2)) // max(len(trainable), 1)))
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    parts = []
+    for v in trainable:
+        flat = v.master.detach().reshape(-1)
+        if flat.numel() > keep:
+            idx = torch.randint(0, flat.numel(), (keep,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    stats = [v.master.detach().reshape(-1).float().cpu() for v in others]
+    if other_elems > budget // 2:
+        stats = [s[:max(1, (budget // 2) // len(stats))] for s in stats]
+    os.makedirs(out_dir, exist_ok=True)
+    cat = lambda ts: torch.cat(ts).numpy() if ts else np.zeros(0, dtype=np.float32)  # noqa: E731
+    np.save(os.path.join(out_dir, "weights.npy"), cat(parts))
+    np.save(os.path.join(out_dir, "moving_stats.npy"), cat(stats))
+    np.save(os.path.join(out_dir, "global_step.npy"), np.array([V.get_global_step().value()], dtype=np.float64))
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss_value], dtype=np.float32))
 
 
 def _ensure_ranks(args):
@@ -173,6 +229,8 @@ def main():
         one = torch.ones(1, dtype=torch.float32, device=dev if dev.type == "cuda" else "cpu")
         dist.all_reduce(one, group=pg)
         comm = {"backend": str(dist.get_backend(pg)), "ranks_in_collective": int(round(float(one.item())))}
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, sess, loss, rank)
     final_loss = float(sess.run(loss))
     if rank == 0:
         ips = world * args.batch * args.steps / elapsed

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One entry point for the GPU-box runs (gpurun -- bash scripts/gpu.sh <what> [tag] [extra args]).
 #   tests   : pytest -m gpu (one process, per-test timeout)
-#   bench   : bench.py (ResNet-50 + BERT-base line), three times
+#   bench   : bench.py --full (ResNet-50 + BERT-base line), three times
 #   prof    : rocprofv3 --kernel-trace --stats of the captured ResNet-50 and BERT-base steps
 #   profr   : the same, ResNet-50 only
 #   pmc     : SQ / FETCH / WRITE+L2 counter passes over both steps (captured steps; PMC_GRAPH=0: eager), each its
@@ -46,7 +46,7 @@ case "$WHAT" in
   bench)
     cd "$ROOT"
     for i in 1 2 3; do
-      timeout -k 10 300 python bench.py "$@" > "$OUT/bench_${TAG}_$i.log" 2>&1 || fail "bench $i" "$OUT/bench_${TAG}_$i.log"
+      timeout -k 10 300 python bench.py --full "$@" > "$OUT/bench_${TAG}_$i.log" 2>&1 || fail "bench $i" "$OUT/bench_${TAG}_$i.log"
       tail -1 "$OUT/bench_${TAG}_$i.log"
     done ;;
   prof)

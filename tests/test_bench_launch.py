@@ -110,6 +110,34 @@ def test_bench_bf16_wire_two_ranks():
 
 
 @pytest.mark.slow
+def test_bench_dump_outputs_repeatable_and_plain_run_is_lean(tmp_path):
+    """``--dump-outputs DIR`` writes the variables the last timed step left as float32/float64 ``.npy`` files of at
+    most 64 MB in all; the same arguments give the same inputs, so two runs (deterministic on the CPU) write the
+    same arrays.  A plain run (no ``--full``) attaches no extra measurement and runs exactly ``--steps`` steps."""
+    import numpy as np
+    recs, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+               "--image_size", "32", "--dump-outputs", str(d)]
+        env = dict(os.environ, OMP_NUM_THREADS="4")
+        env.pop("MDTF_HIP_GRAPH", None)
+        recs.append(_one_json(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)))
+        dumps.append({p.name: np.load(str(p)) for p in sorted(d.iterdir())})
+    rec = recs[0]
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and "extra" not in rec
+    a, b = dumps
+    assert set(a) == {"weights.npy", "moving_stats.npy", "global_step.npy", "loss.npy"} and set(b) == set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["global_step.npy"][0] == 3                  # warmup + steps: --steps really sets the timed steps
+    assert a["weights.npy"].size > 1000000 and a["moving_stats.npy"].size > 0
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.isfinite(a[name]).all(), name
+        assert np.array_equal(a[name], b[name]), name
+    assert a["loss.npy"][0] == pytest.approx(rec["loss_last"], rel=1e-6)
+
+
+@pytest.mark.slow
 def test_async_ps_bench_two_ps_six_workers_cpu():
     """BASELINE config 5's topology (2 ps + 6 workers, one process each) on gloo: every worker reports its
     throughput, every PS its staleness and busy/idle split; the data plane never waits on the store."""
