@@ -17,7 +17,7 @@ from .ops import nn  # noqa: F401
 from .train.variables import (get_variable, variable_scope, name_scope, get_variable_scope, AUTO_REUSE,  # noqa: F401
                               add_to_collection, get_collection, trainable_variables, global_variables,
                               GraphKeys, device, reset_default_graph)
-from .train.step import placeholder  # noqa: F401
+from .train.step import placeholder, clip_by_global_norm, global_norm  # noqa: F401
 from .cluster import ClusterSpec, Server  # noqa: F401
 from . import app  # noqa: F401
 from . import estimator  # noqa: F401

@@ -159,6 +159,8 @@ DEFINE_integer('epochs', 0, "Override @epoch_num when > 0.")
 DEFINE_integer('save_checkpoint_steps', 0, "Checkpoint every N global steps (0: every save_checkpoint_secs).")
 DEFINE_integer('save_checkpoint_secs', 600, "Checkpoint period in seconds (chief), as MonitoredTrainingSession.")
 DEFINE_boolean('hip_graph', False, "Capture the synchronous training step in a hipGraph and replay it (mdtf.train.graph).")
+DEFINE_float('clip_norm', 0.0, "Clip the averaged gradient by this global norm (tf.clip_by_global_norm) when the "
+             "optimizer sets no global_clipnorm of its own; 0: off.")
 
 
 def apply_thread_flags():

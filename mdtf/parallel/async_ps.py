@@ -392,8 +392,21 @@ def run_parameter_server(op, server, sync_replicas=None, total_step=None):
 # ---------------------------------------------------------------------------
 # worker side
 # ---------------------------------------------------------------------------
+def reject_clipping(optimizer, grads_and_vars=()):
+    """The async / sync_ps data plane has no global-norm clip (a worker would have to clip before its push):
+    a requested one is an error when the worker starts, not a silently unclipped run."""
+    asked = bool(getattr(optimizer, "global_clipnorm", None)) or any(
+        getattr(g, "clip", None) is not None for g, _ in grads_and_vars)
+    if asked:
+        raise NotImplementedError("gradient clipping by global norm (global_clipnorm / --clip_norm / "
+                                  "clip_by_global_norm) is not implemented for ps_mode=async|sync_ps; use the "
+                                  "synchronous modes (ps_mode=sync|allreduce|sharded) or remove the clip")
+
+
 class AsyncWorker(object):
     def __init__(self, op, server, tower, grads_and_vars, total_step, sync=False):
+        grads_and_vars = list(grads_and_vars)
+        reject_clipping(getattr(op, "optimizer", None), grads_and_vars)
         self.op = op
         self.sync = sync                  # sync_ps: wait for the PS reply before the next step (no pipelining)
         self.server = server

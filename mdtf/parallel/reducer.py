@@ -563,6 +563,14 @@ class GradReducer(object):
                 self._shards[id(g)]["grad"].copy_(self._gather_index(g, g.grad))
         return 1.0 / self.num_contributors
 
+    def all_reduce_sum(self, t):
+        """SUM all-reduce of a small tensor over the replicas, issued like the bucket collectives (the current
+        stream waits for it; inside a hipGraph capture it is captured).  The global-norm clip sums the sharded
+        replicas' fp64 sums of squares with it; all-reduce gives every rank the same bits."""
+        if self.collective:
+            dist.all_reduce(t, group=self.pg, async_op=True).wait()
+        return t
+
     def _gather_index(self, g, full):
         # world == 1: the shard is the whole bucket (minus nothing)
         return torch.cat([full[b.start:b.end] for b in g.buckets])

@@ -85,6 +85,11 @@ class Train(object):
 
         # -------------------------------------------------------- worker role
         store = configure_store_for(server)
+        if FLAGS.clip_norm and FLAGS.clip_norm > 0 and not getattr(self.optimizer, "global_clipnorm", None):
+            self.optimizer.global_clipnorm = float(FLAGS.clip_norm)      # --clip_norm (the optimizer's own wins)
+        if ps_mode in ("async", "sync_ps"):
+            from ..parallel.async_ps import reject_clipping
+            reject_clipping(self.optimizer)
         pre_train_result = None if pre_fn is None else pre_fn(args, kwargs)
         global_step = V.get_or_create_global_step()
         worker_device = "/job:worker/task:%d" % self.task_index

@@ -20,6 +20,9 @@ Protocol (:class:`StepGraph`, driven by :class:`mdtf.train.step.TrainOp`):
    per-step hyper-parameters (LR schedule, Adam bias correction, gradient
    scale) are read by the optimizer kernels from a device buffer ``dyn``
    (``csrc/optim.hip``), so the captured kernel arguments never go stale.
+   With a global-norm clip (``mdtf.train.clip_by_global_norm``) the captured
+   finalize kernel reads ``dyn`` as its base and the updates read the
+   effective buffer it writes (``csrc/gradnorm.hip``): same refresh, no re-capture.
 3. Replay: copy the new batch into the static buffers (skipped when the
    loader hands out the same device tensors, e.g. synthetic data), refresh
    ``dyn`` if a value changed, ``graph.replay()``.

@@ -24,14 +24,28 @@ def _lr_value(lr, global_step):
     return float(lr)
 
 
+def _clipnorm(value):
+    if value is None:
+        return None
+    value = float(value)
+    if value < 0 or value != value:
+        raise ValueError("global_clipnorm must be a non-negative number, got %r" % (value,))
+    return value or None
+
+
 class Optimizer(object):
     slot_names = ()
 
-    def __init__(self, learning_rate, use_locking=False, name="Optimizer", weight_decay=0.0):
+    def __init__(self, learning_rate, use_locking=False, name="Optimizer", weight_decay=0.0, global_clipnorm=None):
         self._lr = learning_rate
         self._name = name
         self.use_locking = use_locking
         self.weight_decay = float(weight_decay)
+        # clip the averaged gradient by its global norm (tf.clip_by_global_norm, mdtf.train.clip_by_global_norm)
+        # in every train op of this optimizer: for minimize() / the annotation-configured run loop / an
+        # Estimator model_fn, which never expose the gradients.  None or 0: off.
+        self.global_clipnorm = _clipnorm(global_clipnorm)
+        self.last_global_norm = None    # [norm, coef] tensor of the last clipped step (set by the train op)
 
     def get_name(self):
         return self._name
@@ -87,8 +101,10 @@ class Optimizer(object):
 
 
 class GradientDescentOptimizer(Optimizer):
-    def __init__(self, learning_rate, use_locking=False, name="GradientDescent", weight_decay=0.0):
-        super(GradientDescentOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay)
+    def __init__(self, learning_rate, use_locking=False, name="GradientDescent", weight_decay=0.0,
+                 global_clipnorm=None):
+        super(GradientDescentOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay,
+                                                       global_clipnorm)
 
     def update(self, target, lr, grad_scale, step, dyn=None):
         K.sgd_(target.master, target.grad, target.shadow, lr, grad_scale, self._wd(target), dyn=dyn)
@@ -101,8 +117,8 @@ class GradientDescentOptimizer(Optimizer):
 
 class MomentumOptimizer(Optimizer):
     def __init__(self, learning_rate, momentum=0.9, use_locking=False, name="Momentum", use_nesterov=False,
-                 weight_decay=0.0):
-        super(MomentumOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay)
+                 weight_decay=0.0, global_clipnorm=None):
+        super(MomentumOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay, global_clipnorm)
         self.momentum = float(momentum)
         self.use_nesterov = use_nesterov
 
@@ -122,8 +138,8 @@ class MomentumOptimizer(Optimizer):
 
 class AdamOptimizer(Optimizer):
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, use_locking=False, name="Adam",
-                 weight_decay=0.0, decoupled_weight_decay=False, bias_correction=True):
-        super(AdamOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay)
+                 weight_decay=0.0, decoupled_weight_decay=False, bias_correction=True, global_clipnorm=None):
+        super(AdamOptimizer, self).__init__(learning_rate, use_locking, name, weight_decay, global_clipnorm)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
         self.decoupled = decoupled_weight_decay
         self.bias_correction = bias_correction
@@ -151,13 +167,16 @@ class AdamOptimizer(Optimizer):
 
 
 class AdamWeightDecayOptimizer(AdamOptimizer):
-    """BERT's optimizer: Adam without bias correction + decoupled weight decay."""
+    """BERT's optimizer: Adam without bias correction + decoupled weight decay.  BERT's recipe around it:
+    ``learning_rate=mdtf.train.polynomial_decay(...)`` (linear warm-up + decay) and ``global_clipnorm=1.0``
+    (``tf.clip_by_global_norm(grads, 1.0)``)."""
 
     def __init__(self, learning_rate, weight_decay_rate=0.01, beta_1=0.9, beta_2=0.999, epsilon=1e-6,
-                 name="AdamWeightDecayOptimizer"):
+                 name="AdamWeightDecayOptimizer", global_clipnorm=None):
         super(AdamWeightDecayOptimizer, self).__init__(learning_rate, beta_1, beta_2, epsilon, name=name,
                                                        weight_decay=weight_decay_rate,
-                                                       decoupled_weight_decay=True, bias_correction=False)
+                                                       decoupled_weight_decay=True, bias_correction=False,
+                                                       global_clipnorm=global_clipnorm)
 
 
 class SyncReplicasOptimizer(Optimizer):
@@ -174,9 +193,11 @@ class SyncReplicasOptimizer(Optimizer):
 
     def __init__(self, opt, replicas_to_aggregate=None, total_num_replicas=None, variable_averages=None,
                  variables_to_average=None, use_locking=False, name="sync_replicas", mode="allreduce",
-                 bucket_bytes=None, overlap=True, hip_graph=None, comm_dtype=None):
+                 bucket_bytes=None, overlap=True, hip_graph=None, comm_dtype=None, global_clipnorm=None):
         super(SyncReplicasOptimizer, self).__init__(opt._lr, use_locking, name, opt.weight_decay)
         self._opt = opt
+        if global_clipnorm is not None:
+            self.global_clipnorm = global_clipnorm      # held by the wrapped optimizer (property below)
         self.replicas_to_aggregate = replicas_to_aggregate
         self.total_num_replicas = total_num_replicas
         self.mode = mode
@@ -185,6 +206,17 @@ class SyncReplicasOptimizer(Optimizer):
         self.hip_graph = hip_graph   # None: MDTF_HIP_GRAPH / --hip_graph decide (mdtf.train.graph)
         # gradient wire dtype: None -> MDTF_COMM_DTYPE (fp32 default) | "bf16" (mdtf.parallel.reducer)
         self.comm_dtype = comm_dtype
+
+    @property
+    def global_clipnorm(self):
+        opt = self.__dict__.get("_opt")
+        return opt.global_clipnorm if opt is not None else None
+
+    @global_clipnorm.setter
+    def global_clipnorm(self, value):
+        opt = self.__dict__.get("_opt")
+        if opt is not None:
+            opt.global_clipnorm = _clipnorm(value)
 
     def learning_rate(self, global_step=0):
         return self._opt.learning_rate(global_step)
@@ -217,6 +249,28 @@ class SyncReplicasOptimizer(Optimizer):
 
     def get_chief_queue_runner(self):
         return None
+
+
+def polynomial_decay(learning_rate, decay_steps, end_learning_rate=0.0, power=1.0, warmup_steps=0):
+    """``tf.train.polynomial_decay`` with BERT's linear warm-up (``optimization.py``), as a callable of
+    ``global_step`` to pass as an optimizer's ``learning_rate``::
+
+        step <  warmup_steps:  learning_rate * step / warmup_steps
+        else:                  (learning_rate - end) * (1 - min(step, decay_steps) / decay_steps) ** power + end
+
+    The per-step value reaches a replayed hipGraph through the device hyper-parameter buffer (no re-capture)."""
+    lr0, end, power = float(learning_rate), float(end_learning_rate), float(power)
+    decay_steps, warmup_steps = int(decay_steps), int(warmup_steps)
+    if decay_steps <= 0:
+        raise ValueError("decay_steps must be positive, got %r" % (decay_steps,))
+
+    def schedule(global_step):
+        step = int(global_step)
+        if step < warmup_steps:
+            return lr0 * step / warmup_steps
+        frac = 1.0 - min(step, decay_steps) / float(decay_steps)
+        return (lr0 - end) * frac ** power + end
+    return schedule
 
 
 # aliases with TF spellings

@@ -235,6 +235,124 @@ class GradRef(Fetchable):
         return _host_value(self.var.grad)
 
 
+class GlobalNormClip(object):
+    """What one ``clip_by_global_norm`` / ``global_norm`` call (or an optimizer's ``global_clipnorm``) asks of
+    the train op its gradients end up in: the global norm of the averaged gradient, and — ``clip_norm > 0`` —
+    the clip.  ``norm`` is the fetchable handle; ``op`` the TrainOp that adopted it."""
+
+    def __init__(self, clip_norm=0.0):
+        self.clip_norm = float(clip_norm or 0.0)
+        if self.clip_norm != self.clip_norm:
+            raise ValueError("clip_norm must be a number, got NaN")
+        self.norm = GlobalNorm(self)
+        self.op = None
+
+
+class GlobalNorm(Fetchable):
+    """The pre-clip global norm of the step its train op ran in this ``run``: a Python float on the CPU, a
+    cloned 0-dim device tensor on the GPU (no host sync, like a fetched loss under graph replay)."""
+
+    def __init__(self, clip):
+        self.clip = clip
+        self.name = "global_norm"
+
+    def evaluate(self, ctx):
+        key = ("gnorm", id(self.clip))
+        if key not in ctx.cache:
+            raise RuntimeError("global_norm is the norm of a training step's gradient: fetch it in the same run() "
+                               "as the train op its gradients were applied by")
+        return ctx.cache[key]
+
+
+class ClippedGrad(GradRef):
+    """A gradient handle returned by ``clip_by_global_norm``: the variable's flat grad slot, scaled inside the
+    fused update by the coefficient of the shared :class:`GlobalNormClip`."""
+
+    def __init__(self, var, program, clip):
+        super(ClippedGrad, self).__init__(var, program)
+        self.clip = clip
+
+
+def _grad_handles(t_list, what):
+    t_list = list(t_list)
+    for g in t_list:
+        if g is not None and not isinstance(g, GradRef):
+            raise TypeError("%s expects the gradient handles returned by compute_gradients, got %r" % (what, g))
+    if not any(g is not None for g in t_list):
+        raise ValueError("%s: no gradients" % what)
+    return t_list
+
+
+def clip_by_global_norm(t_list, clip_norm, use_norm=None, name=None):
+    """``tf.clip_by_global_norm``: returns ``(list_clipped, global_norm)``.
+
+    ``t_list`` are the gradient handles of ``compute_gradients``; the returned handles stand for
+    ``g * clip_norm / max(global_norm, clip_norm)`` and go to ``apply_gradients`` (also through
+    ``SyncReplicasOptimizer`` and ``Tower.average_gradients``).  The norm is that of the AVERAGED gradient the
+    optimizer applies (after the cross-replica / multi-tower mean), computed on the device between the end of
+    the gradient reduction and the fused updates; ``global_norm`` is fetchable beside the train op.  A train op
+    takes either all of its gradients from one call or none (the flat update has one scale, not one per
+    variable): anything else raises ``ValueError`` when the train op is built.
+
+    Differences from TF: non-decoupled (L2) ``weight_decay`` is added by the update kernels after the clip, so
+    it is not part of the norm (decoupled decay, BERT's case, is exact); with a clip the optimizer runs after
+    the whole backward (sharded mode loses its in-backward update / all-gather overlap)."""
+    if use_norm is not None:
+        raise NotImplementedError("clip_by_global_norm(use_norm=...) is not supported: the norm is computed on the "
+                                  "device inside the training step")
+    t_list = _grad_handles(t_list, "clip_by_global_norm")
+    if float(clip_norm) <= 0:
+        raise ValueError("clip_norm must be positive, got %r (global_norm() computes the norm alone)" % (clip_norm,))
+    if any(getattr(g, "clip", None) is not None and g.clip.clip_norm > 0 for g in t_list if g is not None):
+        raise ValueError("these gradients are already clipped by global norm")
+    clip = GlobalNormClip(clip_norm)
+    return [None if g is None else ClippedGrad(g.var, g.program, clip) for g in t_list], clip.norm
+
+
+def global_norm(t_list, name=None):
+    """``tf.global_norm`` of gradient handles: the fetchable norm, nothing clipped.  The handles are marked, so
+    the train op they are applied by computes the norm; for handles from ``clip_by_global_norm`` this is that
+    call's (pre-clip) norm."""
+    t_list = _grad_handles(t_list, "global_norm")
+    clips = {id(g.clip): g.clip for g in t_list if g is not None and getattr(g, "clip", None) is not None}
+    if len(clips) > 1:
+        raise ValueError("global_norm over gradients of different clip_by_global_norm calls")
+    if clips and all(getattr(g, "clip", None) is not None for g in t_list if g is not None):
+        return list(clips.values())[0].norm
+    if clips:
+        raise ValueError("global_norm over a list of which only some gradients are clipped")
+    clip = GlobalNormClip(0.0)
+    for g in t_list:
+        if g is not None:
+            g.clip = clip
+    return clip.norm
+
+
+def _clip_of(optimizer, grads_and_vars):
+    """The one GlobalNormClip of a train op (None: none requested)."""
+    grads = [g for g, _ in grads_and_vars if g is not None]
+    clips = {}
+    for g in grads:
+        c = getattr(g, "clip", None)
+        if c is not None:
+            clips[id(c)] = c
+    if len(clips) > 1:
+        raise ValueError("the gradients of one train op come from different clip_by_global_norm / global_norm "
+                         "calls: the flat update applies ONE scale")
+    kw = getattr(optimizer, "global_clipnorm", None)
+    if clips:
+        if any(getattr(g, "clip", None) is None for g in grads):
+            raise ValueError("only some gradients of this train op went through clip_by_global_norm / global_norm: "
+                             "partial clipping needs per-variable scales, which the flat update does not have")
+        clip = list(clips.values())[0]
+        if kw and clip.clip_norm > 0:
+            raise ValueError("gradients clipped by clip_by_global_norm applied by an optimizer with global_clipnorm")
+        if kw:
+            clip.clip_norm = float(kw)
+        return clip
+    return GlobalNormClip(kw) if kw else None
+
+
 def compute_gradients(loss, var_list=None):
     if not isinstance(loss, StepTensor):
         raise TypeError("compute_gradients expects the loss handle returned by a Tower/TowerProgram")
@@ -267,6 +385,13 @@ class TrainOp(Fetchable):
         self.grad_scale_extra = 1.0 / max(len(self.programs), 1)
         self.last_contributed = True
         self.graph = None
+        # global-norm clip / norm request (clip_by_global_norm, global_norm, the optimizer's global_clipnorm):
+        # None leaves the step exactly as it is without one
+        self.clip = _clip_of(optimizer, self.grads_and_vars)
+        if self.clip is not None:
+            self.clip.op = self
+        self._norm_buf = None           # ops.gradnorm.NormBuffers, allocated by the first (eager) step
+        self.last_global_norm = None    # device/CPU tensor [norm, coef] of the last step
         _register(self)
 
     # -- finalisation: flat buffers + reducer ----------------------------
@@ -317,11 +442,13 @@ class TrainOp(Fetchable):
         red = self.reducer
         red.begin_step()
         lr = self.optimizer.learning_rate(step)
-        if red.R == red.world:
+        if red.R == red.world and self.clip is None:
             # sharded mode: buckets are updated + all-gathered during backward with the (known) 1/N scale
             pre_scale = (1.0 / red.world) * self.grad_scale_extra
             red.set_update_fn(lambda t: self.optimizer.update(t, lr, pre_scale, self.step_count, dyn=dyn))
         else:
+            # backup workers (scale known after backward) and a global-norm clip (norm known after the last
+            # gradient): every update runs after the whole backward
             red.set_update_fn(None)
         red.fork_update_stream()               # inside a capture: the side stream of the in-backward updates
         _conv._WT.step_begin()                 # conv filters' K-contiguous copies: one batched refresh per step
@@ -337,10 +464,40 @@ class TrainOp(Fetchable):
             _gemm._CATS.step_end()
         scale = red.end_backward(step) * self.grad_scale_extra
         with torch.no_grad():
-            for target in red.update_targets():
+            targets = red.update_targets()
+            if self.clip is not None:
+                dyn = self._clip_dyn(targets, lr, scale, dyn)
+            for target in targets:
                 self.optimizer.update(target, lr, scale, self.step_count, dyn=dyn)
             red.after_update()
         return scale
+
+    def _clip_dyn(self, targets, lr, scale, dyn):
+        """Global norm of the reduced gradient and the clip coefficient, on the device: one sum-of-squares launch
+        over every update target's gradient (full groups in all-reduce mode, this rank's shards in sharded mode),
+        one finalize launch, and the effective ``[lr, lr_t, grad_scale * coef]`` buffer the fused updates then
+        read as their ``dyn``.  ``dyn`` (the StepGraph's buffer inside a capture) is the finalize kernel's base, so
+        replays pick up LR-schedule changes.  No host read of the norm, in eager mode either.  Sharded replicas
+        each hold 1/N of the gradient: their fp64 sums of squares are all-reduced (on the capture stream inside a
+        capture) between the two halves of the finalize, so every rank computes the same coefficient."""
+        from ..ops import gradnorm as GN
+        red = self.reducer
+        grads = [t.grad for t in targets]
+        buf = self._norm_buf
+        if buf is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("global-norm buffers must be allocated by an eager step before capture")
+            buf = self._norm_buf = GN.NormBuffers(grads)
+        lr_t = self.optimizer.step_size(lr, self.step_count)
+        clip_norm = self.clip.clip_norm
+        GN.grad_sumsq_(grads, buf)
+        if red.mode == "sharded" and red.collective:
+            GN.clip_finalize_(buf, clip_norm, lr, lr_t, scale, dyn=dyn, mode=GN.REDUCE)
+            red.all_reduce_sum(buf.sumsq)
+            GN.clip_finalize_(buf, clip_norm, lr, lr_t, scale, dyn=dyn, mode=GN.COEF)
+        else:
+            GN.clip_finalize_(buf, clip_norm, lr, lr_t, scale, dyn=dyn)
+        return buf.eff
 
     def release_graph(self):
         """Free the captured step graph (and its private memory pool).  Must run before the
@@ -373,6 +530,15 @@ class TrainOp(Fetchable):
         if isinstance(c, torch.Tensor):
             c = c.clone()
         self.last_contributed = c
+        if self.clip is not None:
+            stats = self._norm_buf.stats
+            self.last_global_norm = stats
+            o = self.optimizer
+            while o is not None:
+                o.last_global_norm = stats
+                o = getattr(o, "_opt", None)
+            # a per-step snapshot: the next step / replay rewrites the buffer in place
+            ctx.cache[("gnorm", id(self.clip))] = stats[0].item() if stats.device.type == "cpu" else stats[0].clone()
         self.step_count += 1
         if self.global_step is not None:
             self.global_step.increment()
