@@ -37,6 +37,8 @@ def parse():
     p.add_argument("--bucket_mb", type=int, default=None, help="gradient bucket MiB")
     p.add_argument("--clip_norm", type=float, default=0.0,
                    help="clip the gradient by this global norm (global_clipnorm=; BERT's recipe uses 1.0); 0: off")
+    p.add_argument("--optimizer", default="adamw", choices=["adamw", "lamb"],
+                   help="adamw: AdamWeightDecayOptimizer (the default); lamb: LAMBOptimizer (per-layer trust ratios)")
     p.add_argument("--trace_ops", default=None,
                    help="after the warm-up, profile one step with Python stacks (use --hip_graph 0) into this dir")
     return p.parse_args()
@@ -152,8 +154,8 @@ def main():
         ld = SyntheticBertLoader(args.seq, P, seed=rank)
         ld.batch_size = args.batch
         raw, gt = ld.load_train_batch()
-        base = mdtf.train.AdamWeightDecayOptimizer(1e-4, weight_decay_rate=0.01,
-                                                   global_clipnorm=args.clip_norm if args.clip_norm > 0 else None)
+        opt_cls = mdtf.train.LAMBOptimizer if args.optimizer == "lamb" else mdtf.train.AdamWeightDecayOptimizer
+        base = opt_cls(1e-4, weight_decay_rate=0.01, global_clipnorm=args.clip_norm if args.clip_norm > 0 else None)
         tg = []
         tower = Tower(Net(Bert(args.size, seq_len=args.seq, max_predictions=P)), "tower_0/", tg, raw, gt,
                       BertPretrainingLoss(P), base, batch_size=args.batch)
@@ -232,7 +234,9 @@ def main():
                                      "parallelism": "dp%d" % world,
                                      "grad_sync": "ddp" if args.stock else args.mode,
                                      "clip_norm": args.clip_norm if args.clip_norm > 0 and not args.stock else None,
-                                     "optimizer": "torch AdamW" if args.stock else "AdamWeightDecay (fused)"}}),
+                                     "optimizer": ("torch AdamW" if args.stock else
+                                                   "LAMB (fused, per-layer)" if args.optimizer == "lamb"
+                                                   else "AdamWeightDecay (fused)")}}),
               flush=True)
     if not args.stock:
         sess.close()

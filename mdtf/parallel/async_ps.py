@@ -403,10 +403,19 @@ def reject_clipping(optimizer, grads_and_vars=()):
                                   "synchronous modes (ps_mode=sync|allreduce|sharded) or remove the clip")
 
 
+def reject_layerwise(optimizer):
+    """LAMB / LARS need every variable's norms on the rank that updates it, in one step: the PS applies whatever
+    gradients arrived, a group at a time.  An error when the worker starts, not a run with the wrong update."""
+    if getattr(optimizer, "layerwise", False):
+        raise NotImplementedError("layer-wise optimizers (LAMBOptimizer, LARSOptimizer) are not implemented for "
+                                  "ps_mode=async|sync_ps; use the synchronous modes (ps_mode=sync|allreduce|sharded)")
+
+
 class AsyncWorker(object):
     def __init__(self, op, server, tower, grads_and_vars, total_step, sync=False):
         grads_and_vars = list(grads_and_vars)
         reject_clipping(getattr(op, "optimizer", None), grads_and_vars)
+        reject_layerwise(getattr(op, "optimizer", None))
         self.op = op
         self.sync = sync                  # sync_ps: wait for the PS reply before the next step (no pipelining)
         self.server = server

@@ -1,6 +1,7 @@
 """tf.train-compatible training API."""
 from .optimizer import (Optimizer, GradientDescentOptimizer, MomentumOptimizer, AdamOptimizer,  # noqa: F401
-                        AdamWeightDecayOptimizer, SyncReplicasOptimizer, polynomial_decay)
+                        AdamWeightDecayOptimizer, LAMBOptimizer, LARSOptimizer, SyncReplicasOptimizer,
+                        polynomial_decay)
 from .step import clip_by_global_norm, global_norm  # noqa: F401
 from .session import Session, MonitoredSession, MonitoredTrainingSession, Scaffold, global_variables_initializer  # noqa: F401,E501
 from .hooks import (SessionRunHook, SessionRunArgs, SessionRunContext, SessionRunValues, StopAtStepHook,  # noqa: F401

@@ -9,7 +9,7 @@ Reference: ``@optimizer(optimizer=tf.train.AdamOptimizer(0.001))``
 train op.  Updates are applied by one fused HIP launch per parameter group
 (:mod:`mdtf.ops.optim`).  Optimizer slots keep TF's checkpoint names
 (``<var>/Momentum``, ``<var>/Adam``, ``<var>/Adam_1``, ``beta1_power``,
-``beta2_power``).
+``beta2_power``; LAMB: ``<var>/adam_m``, ``<var>/adam_v``).
 """
 import torch
 from ..ops import optim as K
@@ -35,6 +35,7 @@ def _clipnorm(value):
 
 class Optimizer(object):
     slot_names = ()
+    layerwise = False       # per-layer trust ratios (LAMB, LARS): update_all needs every target's reduced gradient
 
     def __init__(self, learning_rate, use_locking=False, name="Optimizer", weight_decay=0.0, global_clipnorm=None):
         self._lr = learning_rate
@@ -77,6 +78,12 @@ class Optimizer(object):
         """One fused launch over ``target``.  ``dyn``: optional device tensor
         ``[lr, lr_t, grad_scale]`` overriding the scalars (hipGraph replay)."""
         raise NotImplementedError
+
+    def update_all(self, targets, lr, grad_scale, step, dyn=None, reducer=None):
+        """The update of every target of one step.  Layer-wise optimizers override it: their norms span targets'
+        pieces (and, sharded, replicas: ``reducer`` sums them)."""
+        for target in targets:
+            self.update(target, lr, grad_scale, step, dyn=dyn)
 
     def step_size(self, lr, step):
         """The per-step ``lr_t`` the kernel applies (Adam folds its bias correction in)."""
@@ -179,6 +186,124 @@ class AdamWeightDecayOptimizer(AdamOptimizer):
                                                        global_clipnorm=global_clipnorm)
 
 
+class _LayerwiseOptimizer(Optimizer):
+    """LAMB / LARS: ``update_all`` is one norm (or moments) launch per target, ONE ``layer_finalize`` launch over
+    every layer of every target (one block per layer; sharded replicas all-reduce the fp64 sums between its two
+    halves, captured like the bucket collectives) and one apply launch per target (:mod:`mdtf.ops.layerwise`).
+    "Layers" are variables; the ratio applies to those with ``apply_weight_decay`` (rank > 1), the others take the
+    plain step.  ``last_ratios``: the device tensor of the last step's per-layer ratios (layer order:
+    ``last_layer_names``)."""
+    layerwise = True
+
+    def __init__(self, *args, **kwargs):
+        super(_LayerwiseOptimizer, self).__init__(*args, **kwargs)
+        self.last_ratios = None
+        self.last_layer_names = None
+
+    def update(self, target, lr, grad_scale, step, dyn=None):
+        raise NotImplementedError("%s is layer-wise: a variable's norm spans update targets' pieces, use update_all"
+                                  % type(self).__name__)
+
+    def update_multi(self, target, grads, steps, grad_scale=1.0):
+        raise NotImplementedError("%s has no multi-gradient update (ps_mode=async|sync_ps is not supported)"
+                                  % type(self).__name__)
+
+    def _norms(self, lmap, buf, ti, target, grad_scale, dyn):
+        raise NotImplementedError
+
+    def _finalize(self, lmap, buf, grad_scale, dyn, mode):
+        raise NotImplementedError
+
+    def _apply(self, lmap, buf, ti, target, lr, grad_scale, dyn):
+        raise NotImplementedError
+
+    def update_all(self, targets, lr, grad_scale, step, dyn=None, reducer=None):
+        if not targets:
+            return
+        from ..ops import layerwise as LW
+        lmap, buf = LW.state_for(targets, reducer)
+        for ti, target in enumerate(targets):
+            self._norms(lmap, buf, ti, target, grad_scale, dyn)
+        if reducer is not None and reducer.mode == "sharded" and reducer.collective:
+            self._finalize(lmap, buf, grad_scale, dyn, LW.REDUCE)
+            reducer.all_reduce_sum(buf.sums)
+            self._finalize(lmap, buf, grad_scale, dyn, LW.COEF)
+        else:
+            self._finalize(lmap, buf, grad_scale, dyn, LW.FULL)
+        for ti, target in enumerate(targets):
+            self._apply(lmap, buf, ti, target, lr, grad_scale, dyn)
+        self.last_ratios, self.last_layer_names = buf.ratio, lmap.names
+
+
+class LAMBOptimizer(_LayerwiseOptimizer):
+    """LAMB as google-research's TF1 ``LAMBOptimizer`` (no bias correction; the code line of
+    :class:`AdamWeightDecayOptimizer`)::
+
+        m = b1 m + (1 - b1) g ;  v = b2 v + (1 - b2) g^2 ;  u = m / (sqrt(v) + eps) + wd w
+        r = |w| / |u|  if |w| > 0 and |u| > 0 else 1 ;  w -= lr r u
+
+    ``wd`` and ``r`` apply to variables with ``apply_weight_decay`` (rank > 1: not LayerNorm / bias); the others
+    have ``wd = 0``, ``r = 1``.  ``g`` is the averaged gradient, clipped when ``global_clipnorm`` is set (BERT's
+    recipe: ``global_clipnorm=1.0``).  Slots: ``<var>/adam_m``, ``<var>/adam_v``."""
+
+    def __init__(self, learning_rate, weight_decay_rate=0.0, beta_1=0.9, beta_2=0.999, epsilon=1e-6,
+                 name="LAMBOptimizer", global_clipnorm=None):
+        super(LAMBOptimizer, self).__init__(learning_rate, False, name, weight_decay_rate, global_clipnorm)
+        self.beta1, self.beta2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+
+    def _norms(self, lmap, buf, ti, t, grad_scale, dyn):
+        from ..ops import layerwise as LW
+        LW.lamb_moments_(lmap, buf, ti, t.master, t.grad, t.state("m"), t.state("v"), self.beta1, self.beta2,
+                         self.epsilon, grad_scale, self.weight_decay, dyn=dyn)
+
+    def _finalize(self, lmap, buf, grad_scale, dyn, mode):
+        from ..ops import layerwise as LW
+        LW.layer_finalize_(lmap, buf, LW.LAMB, grad_scale=grad_scale, dyn=dyn, mode=mode)
+
+    def _apply(self, lmap, buf, ti, t, lr, grad_scale, dyn):
+        from ..ops import layerwise as LW
+        LW.lamb_apply_(lmap, buf, ti, t.master, t.state("m"), t.state("v"), t.shadow, lr, self.epsilon,
+                       self.weight_decay, dyn=dyn)
+
+    def slot_checkpoint_names(self):
+        return [("m", "adam_m"), ("v", "adam_v")]
+
+
+class LARSOptimizer(_LayerwiseOptimizer):
+    """LARS as ``tf.contrib.opt.LARSOptimizer``::
+
+        decay variables:  t = eeta |w| / (|g| + wd |w| + eps)  if |w| > 0 and |g| > 0 else 1
+                          s = lr t (g + wd w)
+        other variables:  s = lr g
+        acc = momentum acc + s ;  w -= acc          (nesterov: w -= s + momentum acc)
+
+    "Decay variables" are those with ``apply_weight_decay`` (rank > 1), the set LARS's skip list leaves.  ``g``
+    is the averaged (and, with ``global_clipnorm``, clipped) gradient.  Slot: ``<var>/Momentum``."""
+
+    def __init__(self, learning_rate, momentum=0.9, weight_decay=1e-4, eeta=1e-3, epsilon=0.0, use_nesterov=False,
+                 name="LARSOptimizer", global_clipnorm=None):
+        super(LARSOptimizer, self).__init__(learning_rate, False, name, weight_decay, global_clipnorm)
+        self.momentum, self.eeta, self.epsilon = float(momentum), float(eeta), float(epsilon)
+        self.use_nesterov = use_nesterov
+
+    def _norms(self, lmap, buf, ti, t, grad_scale, dyn):
+        from ..ops import layerwise as LW
+        LW.lars_norms_(lmap, buf, ti, t.master, t.grad)
+
+    def _finalize(self, lmap, buf, grad_scale, dyn, mode):
+        from ..ops import layerwise as LW
+        LW.layer_finalize_(lmap, buf, LW.LARS, self.eeta, self.weight_decay, self.epsilon, grad_scale, dyn=dyn,
+                           mode=mode)
+
+    def _apply(self, lmap, buf, ti, t, lr, grad_scale, dyn):
+        from ..ops import layerwise as LW
+        LW.lars_apply_(lmap, buf, ti, t.master, t.grad, t.state("momentum"), t.shadow, lr, self.momentum, grad_scale,
+                       self.weight_decay, self.use_nesterov, dyn=dyn)
+
+    def slot_checkpoint_names(self):
+        return [("momentum", "Momentum")]
+
+
 class SyncReplicasOptimizer(Optimizer):
     """Synchronous data-parallel wrapper (``tf.train.SyncReplicasOptimizer``).
 
@@ -226,6 +351,13 @@ class SyncReplicasOptimizer(Optimizer):
 
     def update_multi(self, target, grads, steps, grad_scale=1.0):
         self._opt.update_multi(target, grads, steps, grad_scale)
+
+    @property
+    def layerwise(self):
+        return self._opt.layerwise
+
+    def update_all(self, targets, lr, grad_scale, step, dyn=None, reducer=None):
+        self._opt.update_all(targets, lr, grad_scale, step, dyn=dyn, reducer=reducer)
 
     def step_size(self, lr, step):
         return self._opt.step_size(lr, step)

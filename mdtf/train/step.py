@@ -392,6 +392,8 @@ class TrainOp(Fetchable):
             self.clip.op = self
         self._norm_buf = None           # ops.gradnorm.NormBuffers, allocated by the first (eager) step
         self.last_global_norm = None    # device/CPU tensor [norm, coef] of the last step
+        self._layer_map = None          # ops.layerwise.LayerMap / LayerBuffers of a layer-wise optimizer (LAMB,
+        self._layer_buf = None          # LARS), allocated by the first (eager) step; None for every other one
         _register(self)
 
     # -- finalisation: flat buffers + reducer ----------------------------
@@ -442,13 +444,14 @@ class TrainOp(Fetchable):
         red = self.reducer
         red.begin_step()
         lr = self.optimizer.learning_rate(step)
-        if red.R == red.world and self.clip is None:
+        if red.R == red.world and self.clip is None and not self.optimizer.layerwise:
             # sharded mode: buckets are updated + all-gathered during backward with the (known) 1/N scale
             pre_scale = (1.0 / red.world) * self.grad_scale_extra
             red.set_update_fn(lambda t: self.optimizer.update(t, lr, pre_scale, self.step_count, dyn=dyn))
         else:
-            # backup workers (scale known after backward) and a global-norm clip (norm known after the last
-            # gradient): every update runs after the whole backward
+            # backup workers (scale known after backward), a global-norm clip (norm known after the last
+            # gradient) and layer-wise optimizers (a variable's norm spans the replicas' shards): every update
+            # runs after the whole backward
             red.set_update_fn(None)
         red.fork_update_stream()               # inside a capture: the side stream of the in-backward updates
         _conv._WT.step_begin()                 # conv filters' K-contiguous copies: one batched refresh per step
@@ -467,8 +470,11 @@ class TrainOp(Fetchable):
             targets = red.update_targets()
             if self.clip is not None:
                 dyn = self._clip_dyn(targets, lr, scale, dyn)
-            for target in targets:
-                self.optimizer.update(target, lr, scale, self.step_count, dyn=dyn)
+            if self.optimizer.layerwise and targets and self._layer_buf is None:
+                from ..ops import layerwise as LW
+                # (raises inside a capture: allocated by the first eager step, like the norm buffers)
+                self._layer_map, self._layer_buf = LW.state_for(targets, red)
+            self.optimizer.update_all(targets, lr, scale, self.step_count, dyn=dyn, reducer=red)
             red.after_update()
         return scale
 
