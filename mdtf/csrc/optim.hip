@@ -19,6 +19,10 @@ namespace {
 
 constexpr int kThreads = 256;
 
+// the kernels move float4 (16 B) of master / gradient / state and 4 bf16 (8 B) of shadow / wire gradient at once;
+// a pointer off that alignment is refused before any launch (null: buffer not given)
+inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 inline int grid_for(long long n4) {
   long long b = ceil_div(n4, kThreads);
   return static_cast<int>(b < 2048 ? (b > 0 ? b : 1) : 2048);
@@ -38,6 +42,28 @@ __device__ __forceinline__ void store_shadow4(bf16_t* s, long long i, const floa
   *reinterpret_cast<uint2*>(s + i) = make_uint2(lo, hi);
 }
 
+// One element of the sgd / momentum / adam update, shared by the single-update kernels and apply_multi_kernel.
+// The fused multiply-adds are written out and contraction is off: every kernel and every build variant must round
+// the same way (k = 1 of the batched apply is bitwise the single launch; MDTF_NT_OPT / MDTF_ADAM_CHUNK change the
+// memory access only).  Left to the compiler, ``w - lr * x`` was fused in the single-update kernels but not in
+// apply_multi_kernel, and Adam's ``g*gs + wd*w`` and ``b2*v + (1-b2)*g*g`` were fused for some lanes of a float4
+// and not for others, differently in the chunked and the grid-stride kernel.
+__device__ __forceinline__ float decayed_grad(float g, float w, float gs, float wd) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(wd, w, g * gs);
+}
+__device__ __forceinline__ void sgd1(float& w, float g, float lr, float gs, float wd) {
+#pragma clang fp contract(off)
+  w = __builtin_fmaf(-lr, decayed_grad(g, w, gs, wd), w);
+}
+__device__ __forceinline__ void momentum1(float& w, float g, float& a, float lr, float mom, float gs, float wd,
+                                          int nesterov) {
+#pragma clang fp contract(off)
+  const float gt = decayed_grad(g, w, gs, wd);
+  a = __builtin_fmaf(mom, a, gt);
+  w = __builtin_fmaf(-lr, nesterov ? __builtin_fmaf(mom, a, gt) : a, w);
+}
+
 __global__ void __launch_bounds__(kThreads) sgd_kernel(long long n, float* __restrict__ w, const float* __restrict__ g,
                                                       bf16_t* __restrict__ shadow, float lr, float gs, float wd,
                                                       const float* __restrict__ dyn) {
@@ -47,10 +73,10 @@ __global__ void __launch_bounds__(kThreads) sgd_kernel(long long n, float* __res
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     float4 wv = reinterpret_cast<float4*>(w)[i];
     float4 gv = reinterpret_cast<const float4*>(g)[i];
-    wv.x -= lr * (gv.x * gs + wd * wv.x);
-    wv.y -= lr * (gv.y * gs + wd * wv.y);
-    wv.z -= lr * (gv.z * gs + wd * wv.z);
-    wv.w -= lr * (gv.w * gs + wd * wv.w);
+    sgd1(wv.x, gv.x, lr, gs, wd);
+    sgd1(wv.y, gv.y, lr, gs, wd);
+    sgd1(wv.z, gv.z, lr, gs, wd);
+    sgd1(wv.w, gv.w, lr, gs, wd);
     reinterpret_cast<float4*>(w)[i] = wv;
     if (shadow) store_shadow4(shadow, i * 4, wv);
   }
@@ -91,23 +117,10 @@ __global__ void __launch_bounds__(kThreads) momentum_kernel(long long n, float* 
     float4 wv = ldf4<NT>(w, i);
     float4 gv = ldf4<NT>(g, i);
     float4 av = ldf4<NT>(acc, i);
-    float gx = gv.x * gs + wd * wv.x, gy = gv.y * gs + wd * wv.y;
-    float gz = gv.z * gs + wd * wv.z, gw = gv.w * gs + wd * wv.w;
-    av.x = mom * av.x + gx;
-    av.y = mom * av.y + gy;
-    av.z = mom * av.z + gz;
-    av.w = mom * av.w + gw;
-    if (nesterov) {
-      wv.x -= lr * (gx + mom * av.x);
-      wv.y -= lr * (gy + mom * av.y);
-      wv.z -= lr * (gz + mom * av.z);
-      wv.w -= lr * (gw + mom * av.w);
-    } else {
-      wv.x -= lr * av.x;
-      wv.y -= lr * av.y;
-      wv.z -= lr * av.z;
-      wv.w -= lr * av.w;
-    }
+    momentum1(wv.x, gv.x, av.x, lr, mom, gs, wd, nesterov);
+    momentum1(wv.y, gv.y, av.y, lr, mom, gs, wd, nesterov);
+    momentum1(wv.z, gv.z, av.z, lr, mom, gs, wd, nesterov);
+    momentum1(wv.w, gv.w, av.w, lr, mom, gs, wd, nesterov);
     stf4<NT>(acc, i, av);
     stf4<NT>(w, i, wv);
     if (shadow) store_shadow4(shadow, i * 4, wv);
@@ -116,12 +129,12 @@ __global__ void __launch_bounds__(kThreads) momentum_kernel(long long n, float* 
 
 __device__ __forceinline__ float adam1(float& w, float g, float& m, float& v, float lr, float lr_t, float b1, float b2,
                                        float eps, float gs, float wd, int decoupled) {
-  g *= gs;
-  if (!decoupled) g += wd * w;
-  m = b1 * m + (1.f - b1) * g;
-  v = b2 * v + (1.f - b2) * g * g;
+#pragma clang fp contract(off)
+  g = decoupled ? g * gs : decayed_grad(g, w, gs, wd);
+  m = __builtin_fmaf(b1, m, (1.f - b1) * g);
+  v = __builtin_fmaf(b2, v, (1.f - b2) * g * g);
   float upd = lr_t * m / (sqrtf(v) + eps);
-  if (decoupled) upd += lr * wd * w;
+  if (decoupled) upd = __builtin_fmaf(lr * wd, w, upd);
   w -= upd;
   return w;
 }
@@ -221,14 +234,10 @@ __global__ void __launch_bounds__(kThreads) apply_multi_kernel(int kind, long lo
       for (int e = 0; e < 4; ++e) {
         if (kind == 2) {
           adam1(wp[e], gp[e], ap[e], vp[e], lr, lr_t, b1, b2, eps, gs, wd, flag);
+        } else if (kind == 1) {
+          momentum1(wp[e], gp[e], ap[e], lr, mom, gs, wd, flag);
         } else {
-          const float g = gp[e] * gs + wd * wp[e];
-          if (kind == 1) {
-            ap[e] = mom * ap[e] + g;
-            wp[e] -= lr * (flag ? g + mom * ap[e] : ap[e]);
-          } else {
-            wp[e] -= lr * g;
-          }
+          sgd1(wp[e], gp[e], lr, gs, wd);
         }
       }
     }
@@ -248,8 +257,10 @@ MDTF_EXPORT int mdtf_fused_apply_multi(int kind, long long n, void* w, void* s1,
                                        float mom, float b1, float b2, float eps, float gs, float wd, int flag,
                                        hipStream_t st) {
   if (n % 4 || k < 1 || k > kMaxMulti || kind < 0 || kind > 2) return MDTF_EINVAL;
+  if (!aligned(w, 16) || !aligned(s1, 16) || !aligned(s2, 16) || !aligned(shadow, 8)) return MDTF_EINVAL;
   MultiGrads mg{};
   for (int u = 0; u < k; ++u) {
+    if (!aligned(grads[u], gbf16 ? 8 : 16)) return MDTF_EINVAL;
     mg.g[u] = grads[u];
     mg.lr[u] = lrs[u];
     mg.lr_t[u] = lr_ts[u];
@@ -260,10 +271,11 @@ MDTF_EXPORT int mdtf_fused_apply_multi(int kind, long long n, void* w, void* s1,
   return 0;
 }
 
-// n must be a multiple of 4 (flat groups are padded to 64 elements).
+// n must be a multiple of 4 (flat groups are padded to 64 elements); master, gradient and state 16-byte aligned,
+// the bf16 shadow 8-byte aligned.
 MDTF_EXPORT int mdtf_fused_sgd(long long n, void* w, const void* g, void* shadow, float lr, float gs, float wd,
                                const void* dyn, hipStream_t st) {
-  if (n % 4) return MDTF_EINVAL;
+  if (n % 4 || !aligned(w, 16) || !aligned(g, 16) || !aligned(shadow, 8) || !aligned(dyn, 4)) return MDTF_EINVAL;
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4)), dim3(kThreads), 0, st, n, (float*)w, (const float*)g,
                      (bf16_t*)shadow, lr, gs, wd, (const float*)dyn);
   MDTF_LAUNCH_CHECK();
@@ -272,7 +284,8 @@ MDTF_EXPORT int mdtf_fused_sgd(long long n, void* w, const void* g, void* shadow
 
 MDTF_EXPORT int mdtf_fused_momentum(long long n, void* w, const void* g, void* acc, void* shadow, float lr, float mom,
                                     float gs, float wd, int nesterov, const void* dyn, hipStream_t st) {
-  if (n % 4) return MDTF_EINVAL;
+  if (n % 4 || !aligned(w, 16) || !aligned(g, 16) || !aligned(acc, 16) || !aligned(shadow, 8) || !aligned(dyn, 4))
+    return MDTF_EINVAL;
   hipLaunchKernelGGL((nt_opt() ? momentum_kernel<true> : momentum_kernel<false>), dim3(grid_for(n / 4)), dim3(kThreads), 0, st, n, (float*)w, (const float*)g,
                      (float*)acc, (bf16_t*)shadow, lr, mom, gs, wd, nesterov, (const float*)dyn);
   MDTF_LAUNCH_CHECK();
@@ -282,7 +295,9 @@ MDTF_EXPORT int mdtf_fused_momentum(long long n, void* w, const void* g, void* a
 MDTF_EXPORT int mdtf_fused_adam(long long n, void* w, const void* g, void* m, void* v, void* shadow, float lr,
                                 float lr_t, float b1, float b2, float eps, float gs, float wd, int decoupled,
                                 const void* dyn, hipStream_t st) {
-  if (n % 4) return MDTF_EINVAL;
+  if (n % 4 || !aligned(w, 16) || !aligned(g, 16) || !aligned(m, 16) || !aligned(v, 16) || !aligned(shadow, 8) ||
+      !aligned(dyn, 4))
+    return MDTF_EINVAL;
   static const bool chunk = [] {
     const char* e = getenv("MDTF_ADAM_CHUNK");
     return !(e && e[0] == '0');

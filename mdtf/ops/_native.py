@@ -90,10 +90,10 @@ _DETERMINISTIC = os.environ.get("MDTF_DETERMINISTIC", "0") not in ("0", "", "fal
 def check(rc, what):
     if rc != 0:
         raise RuntimeError("mdtf kernel %s failed: %s (code %d)" % (what, _error_string(rc), rc))
-    if _SYNC_CHECK and not torch.cuda.is_current_stream_capturing():
+    if _SYNC_CHECK and torch.cuda.is_initialized() and not torch.cuda.is_current_stream_capturing():
         # debug mode (MDTF_SYNC_CHECK=1): serialize after every native launch so a faulting
-        # kernel is named here instead of surfacing at some later synchronization
-        import torch
+        # kernel is named here instead of surfacing at some later synchronization (a process that never
+        # initialised the GPU launched nothing)
         try:
             torch.cuda.synchronize()
         except RuntimeError as e:
@@ -120,12 +120,15 @@ def set_sync_check(flag=True):
     _SYNC_CHECK = bool(flag)
 
 
+_STATUS = {-1: "invalid argument", -2: "unsupported configuration"}        # MdtfStatus (include/mdtf_common.h)
+
+
 def _error_string(rc):
     try:
         s = _lib.mdtf_error_string(ctypes.c_int(rc))
         return s.decode() if s else "?"
-    except Exception:  # pragma: no cover
-        return "?"
+    except Exception:       # library not loaded (a CPU-only caller): the library's own codes are still named
+        return _STATUS.get(rc, "?")
 
 
 # ---------------------------------------------------------------------------

@@ -15,6 +15,7 @@ CPU tensors use the vectorised PyTorch reference below (same math).
 kernels read instead of their scalar arguments, so a hipGraph-captured step
 (:mod:`mdtf.train.graph`) picks up per-step values without re-capture.
 """
+import ctypes
 import math
 
 import torch
@@ -36,6 +37,12 @@ def _shadow_code(shadow):
 
 def _native_ok(master):
     return master.is_cuda and _native.mode() != "torch" and _native.use_native(master)
+
+
+def _one_minus(beta):
+    """``1 - beta`` as the kernels (and TF's fp32 ``ApplyAdam``) form it: from the fp32 value of ``beta``.  In
+    double, ``1 - 0.999`` differs from that by 1.3e-5 relative, which goes straight into ``v``."""
+    return 1.0 - ctypes.c_float(beta).value
 
 
 def _dyn_scalars(dyn, lr, lr_t, grad_scale):
@@ -112,8 +119,8 @@ def adam_(master, grad, m, v, shadow, lr, beta1, beta2, epsilon, step, grad_scal
     g = grad.float() * grad_scale
     if weight_decay and not decoupled:
         g = g + weight_decay * master
-    m.mul_(beta1).add_(g, alpha=1 - beta1)
-    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    m.mul_(beta1).add_(g, alpha=_one_minus(beta1))
+    v.mul_(beta2).addcmul_(g, g, value=_one_minus(beta2))
     upd = lr_t * m / (v.sqrt() + epsilon)
     if weight_decay and decoupled:
         upd = upd + lr * weight_decay * master
@@ -138,7 +145,6 @@ def apply_multi_(kind, master, grads, s1, s2, shadow, lrs, lr_ts, momentum=0.0, 
     k = len(grads)
     assert 1 <= k <= MAX_MULTI and len(lrs) == k and len(lr_ts) == k
     if _native_ok(master) and all(g.dtype == grads[0].dtype for g in grads):
-        import ctypes
         gp = (ctypes.c_void_p * k)(*[g.data_ptr() for g in grads])
         fl = (ctypes.c_float * k)(*[float(x) for x in lrs])
         ft = (ctypes.c_float * k)(*[float(x) for x in lr_ts])
@@ -153,8 +159,8 @@ def apply_multi_(kind, master, grads, s1, s2, shadow, lrs, lr_ts, momentum=0.0, 
         if kind == "adam":
             if weight_decay and not flag:
                 g = g + weight_decay * master
-            s1.mul_(beta1).add_(g, alpha=1 - beta1)
-            s2.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            s1.mul_(beta1).add_(g, alpha=_one_minus(beta1))
+            s2.mul_(beta2).addcmul_(g, g, value=_one_minus(beta2))
             upd = lr_t * s1 / (s2.sqrt() + epsilon)
             if weight_decay and flag:
                 upd = upd + lr * weight_decay * master
