@@ -161,6 +161,8 @@ DEFINE_integer('save_checkpoint_secs', 600, "Checkpoint period in seconds (chief
 DEFINE_boolean('hip_graph', False, "Capture the synchronous training step in a hipGraph and replay it (mdtf.train.graph).")
 DEFINE_float('clip_norm', 0.0, "Clip the averaged gradient by this global norm (tf.clip_by_global_norm) when the "
              "optimizer sets no global_clipnorm of its own; 0: off.")
+DEFINE_float('moving_average_decay', 0.0, "Keep tf.train.ExponentialMovingAverage(decay, num_updates=global_step) of "
+             "the weights while training; Eval then evaluates the averaged weights; 0: off.")
 
 
 def apply_thread_flags():

@@ -411,11 +411,22 @@ def reject_layerwise(optimizer):
                                   "ps_mode=async|sync_ps; use the synchronous modes (ps_mode=sync|allreduce|sharded)")
 
 
+def reject_moving_average(decay):
+    """The weights live on the PS ranks, which run no train op to attach an average to: a requested one
+    (``--moving_average_decay`` / the run loop's ``moving_average_decay``) is an error when the worker starts, not a
+    run that silently keeps none."""
+    if decay and float(decay) > 0:
+        raise NotImplementedError("ExponentialMovingAverage of the weights (--moving_average_decay) is not "
+                                  "implemented for ps_mode=async|sync_ps; use the synchronous modes "
+                                  "(ps_mode=sync|allreduce|sharded) or set it to 0")
+
+
 class AsyncWorker(object):
     def __init__(self, op, server, tower, grads_and_vars, total_step, sync=False):
         grads_and_vars = list(grads_and_vars)
         reject_clipping(getattr(op, "optimizer", None), grads_and_vars)
         reject_layerwise(getattr(op, "optimizer", None))
+        reject_moving_average(getattr(op, "moving_average_decay", None))
         self.op = op
         self.sync = sync                  # sync_ps: wait for the PS reply before the next step (no pipelining)
         self.server = server

@@ -578,6 +578,12 @@ class GradReducer(object):
     def update_targets(self):
         if self.eager_update is not None and all(getattr(b, "updated", False) for b in self.space.buckets):
             return []                           # every bucket was updated during backward
+        return self.all_targets()
+
+    def all_targets(self):
+        """Every group's update target (full buffers in all-reduce mode, this rank's shards in sharded mode),
+        whether or not the buckets were already updated during backward: what per-target state that is not part
+        of the optimizer's update (the weights' moving average) runs over after the step's updates."""
         out = []
         for g in self.space.groups:
             if self.mode == "allreduce":
@@ -618,12 +624,14 @@ class GradReducer(object):
             w.wait()
 
     # -- full-state helpers -------------------------------------------------
-    def gather_full_master(self):
-        """Make every rank's full fp32 master current (checkpointing, eval)."""
+    def gather_full_master(self, include_fp32=False):
+        """Make every rank's full fp32 master current (checkpointing, eval).  ``include_fp32``: also the groups
+        without a shadow, whose gather is otherwise part of every step (for a caller that rewrote the master shards
+        outside a step: the exchange with the weights' moving average)."""
         if self.mode != "sharded":
             return
         for g in self.space.groups:
-            if g.shadow is None:
+            if g.shadow is None and not include_fp32:
                 continue  # fp32 groups are gathered every step
             sh = self._shards[id(g)]
             for b in g.buckets:

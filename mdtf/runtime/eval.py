@@ -45,7 +45,7 @@ class Eval(object):
         V.get_or_create_global_step()
         ckpt = self._wait_for_checkpoint()
         if ckpt is not None:
-            SV.Saver(save_optimizer_state=False).restore(None, ckpt)
+            self._restore(ckpt)
             logger.info("Eval: restored %s (global_step %d)" % (ckpt, V.get_global_step().value()))
         else:
             logger.warn("Eval: no checkpoint in %r; evaluating the initial weights" % (self.model_dir,))
@@ -86,6 +86,26 @@ class Eval(object):
         if post_eval_fn is not None:
             post_eval_fn(args, kwargs)
         return self.metrics
+
+    def _restore(self, ckpt):
+        """--moving_average_decay (or the ``moving_average_decay`` attribute): restore every trainable variable
+        from its ``<var>/ExponentialMovingAverage`` entry, i.e. evaluate the averaged weights; a checkpoint
+        written without averages is evaluated on its raw weights, with a warning."""
+        decay = getattr(self, "moving_average_decay", None)         # an attribute of 0 switches a set flag off
+        decay = float((FLAGS.moving_average_decay if decay is None else decay) or 0.0)
+        self.evaluated_averages = False
+        if decay > 0:
+            from ..ckpt.tensor_bundle import BundleReader
+            from ..train.moving_averages import ExponentialMovingAverage
+            ema = ExponentialMovingAverage(decay)
+            reader = BundleReader(ckpt)
+            wanted = [ema.average_name(v) for v in V.get_store().trainable_variables()]
+            if wanted and all(k in reader for k in wanted):
+                SV.Saver(ema.variables_to_restore()).restore(None, ckpt, reader=reader)
+                self.evaluated_averages = True
+                return
+            logger.warn("Eval: %s holds no moving averages (%s/...): evaluating the raw weights" % (ckpt, ema.name))
+        SV.Saver(save_optimizer_state=False).restore(None, ckpt)
 
     def _wait_for_checkpoint(self):
         md = getattr(self, "model_dir", None)

@@ -87,9 +87,14 @@ class Train(object):
         store = configure_store_for(server)
         if FLAGS.clip_norm and FLAGS.clip_norm > 0 and not getattr(self.optimizer, "global_clipnorm", None):
             self.optimizer.global_clipnorm = float(FLAGS.clip_norm)      # --clip_norm (the optimizer's own wins)
+        # --moving_average_decay (the run loop's own attribute wins): tf.train.ExponentialMovingAverage of the weights
+        ma_decay = getattr(self, "moving_average_decay", None)      # an attribute of 0 switches a set flag off
+        ma_decay = float((FLAGS.moving_average_decay if ma_decay is None else ma_decay) or 0.0)
+        self.moving_average_decay = ma_decay
         if ps_mode in ("async", "sync_ps"):
-            from ..parallel.async_ps import reject_clipping
+            from ..parallel.async_ps import reject_clipping, reject_moving_average
             reject_clipping(self.optimizer)
+            reject_moving_average(ma_decay)
         pre_train_result = None if pre_fn is None else pre_fn(args, kwargs)
         global_step = V.get_or_create_global_step()
         worker_device = "/job:worker/task:%d" % self.task_index
@@ -117,6 +122,10 @@ class Train(object):
         optimizer = O.SyncReplicasOptimizer(self.optimizer, replicas_to_aggregate=replicas_to_aggregate,
                                             total_num_replicas=num_replicas, name="sync_replicas", mode=ps_mode)
         train_op = optimizer.apply_gradients(grads, global_step=global_step)
+        if ma_decay > 0:
+            from ..train.moving_averages import ExponentialMovingAverage
+            ExponentialMovingAverage(ma_decay, num_updates=global_step).apply(train_op=train_op)
+        self.train_op = train_op
         sync_replicas_hook = optimizer.make_session_run_hook(is_chief)
 
         if is_chief:

@@ -3,6 +3,7 @@ from .optimizer import (Optimizer, GradientDescentOptimizer, MomentumOptimizer, 
                         AdamWeightDecayOptimizer, LAMBOptimizer, LARSOptimizer, SyncReplicasOptimizer,
                         polynomial_decay)
 from .step import clip_by_global_norm, global_norm  # noqa: F401
+from .moving_averages import ExponentialMovingAverage  # noqa: F401
 from .session import Session, MonitoredSession, MonitoredTrainingSession, Scaffold, global_variables_initializer  # noqa: F401,E501
 from .hooks import (SessionRunHook, SessionRunArgs, SessionRunContext, SessionRunValues, StopAtStepHook,  # noqa: F401
                     StepCounterHook, CheckpointSaverHook, SummarySaverHook, ExamplesPerSecondHook,

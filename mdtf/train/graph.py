@@ -23,6 +23,8 @@ Protocol (:class:`StepGraph`, driven by :class:`mdtf.train.step.TrainOp`):
    With a global-norm clip (``mdtf.train.clip_by_global_norm``) the captured
    finalize kernel reads ``dyn`` as its base and the updates read the
    effective buffer it writes (``csrc/gradnorm.hip``): same refresh, no re-capture.
+   A moving average of the weights (``mdtf.train.ExponentialMovingAverage``) keeps its
+   ``1 - decay`` in a 1-float device buffer of its own, refreshed the same way.
 3. Replay: copy the new batch into the static buffers (skipped when the
    loader hands out the same device tensors, e.g. synthetic data), refresh
    ``dyn`` if a value changed, ``graph.replay()``.
@@ -308,6 +310,8 @@ class StepGraph(object):
             host = torch.tensor(vals, dtype=torch.float32).pin_memory()
             self.dyn.copy_(host, non_blocking=True)
             self._dyn_vals = vals
+        if op.ema is not None:
+            op.ema.device_omd(step)     # the moving average's 1 - decay of this step: copied only when it changed
 
     def _capture(self, ctx, step):
         from .step import RunContext

@@ -2,7 +2,10 @@
 
 Saved tensors use TF names: variables by scope path, ``global_step``
 (int64), optimizer slots ``<var>/Momentum`` or ``<var>/Adam``/``<var>/Adam_1``
-and the Adam ``beta1_power``/``beta2_power`` scalars.  With ``sharded=True``
+and the Adam ``beta1_power``/``beta2_power`` scalars, and the weights' moving
+averages ``<var>/ExponentialMovingAverage`` of a train op that keeps them
+(``mdtf.train.ExponentialMovingAverage``).  A dict ``var_list`` maps checkpoint
+names to variables, as in TF.  With ``sharded=True``
 one data file per PS task is written and each variable goes to the shard of
 the PS task ``replica_device_setter`` assigned it to (the reference's PS
 variable placement, ``distribute_train.py:109-110``).
@@ -67,14 +70,27 @@ class Saver(object):
         self.save_optimizer_state = save_optimizer_state
         self._last = []
 
-    def _variables(self):
+    def _by_name(self):
+        """A dict ``var_list`` (TF's meaning: checkpoint name -> variable, e.g.
+        ``ExponentialMovingAverage.variables_to_restore()``): exactly these entries are saved / restored, under the
+        keys; no optimizer slots or averages beside them."""
+        return isinstance(self.var_list, dict)
+
+    def _named_variables(self):
+        """(checkpoint name, Variable or GlobalStep) pairs."""
         store = V.get_store()
         if self.var_list is None:
-            return store.global_variables()
+            return [(v.name, v) for v in store.global_variables()]
+        if self._by_name():
+            return [(k, store.vars[v] if isinstance(v, str) else v) for k, v in self.var_list.items()]
         out = []
-        for v in (self.var_list.values() if isinstance(self.var_list, dict) else self.var_list):
-            out.append(store.vars[v] if isinstance(v, str) else v)
+        for v in self.var_list:
+            v = store.vars[v] if isinstance(v, str) else v
+            out.append((v.name, v))
         return out
+
+    def _variables(self):
+        return [v for _, v in self._named_variables() if not isinstance(v, V.GlobalStep)]
 
     def _named_tensors(self):
         """name -> (tensor, ps_shard).  Collective in PS-shard mode."""
@@ -83,10 +99,25 @@ class Saver(object):
         for op in S.train_ops():
             if op.reducer is not None:
                 op.reducer.gather_full_master()
-        for v in self._variables():
-            tensors[v.name] = (v.master, v.ps_task or 0)
+        for name, v in self._named_variables():
+            if isinstance(v, V.GlobalStep):
+                tensors[name] = (torch.tensor(v.value(), dtype=torch.int64), 0)
+            else:
+                tensors[name] = (v.master, v.ps_task or 0)
+        if self._by_name():
+            return tensors
         if V.get_global_step() is not None:
             tensors["global_step"] = (torch.tensor(step, dtype=torch.int64), 0)
+        # the weights' moving averages are model variables in TF (<var>/ExponentialMovingAverage): written
+        # whatever save_optimizer_state says
+        for op in S.train_ops():
+            if op.reducer is None or op.ema is None:
+                continue
+            fulls = op.ema.full_state()
+            for g, full in zip(op.space.groups, fulls):
+                for var in g.variables:
+                    o = var.flat_offset
+                    tensors[op.ema.average_name(var)] = (full[o:o + var.numel()].view(var.shape), var.ps_task or 0)
         if self.save_optimizer_state:
             for op in S.train_ops():
                 if op.reducer is None:
@@ -140,18 +171,34 @@ class Saver(object):
         store = V.get_store()
         missing = []
         with torch.no_grad():
-            for v in self._variables():
-                if v.name in r:
-                    v.master.copy_(r.get_tensor(v.name).to(v.master.dtype).to(v.master.device))
+            by_name = self._by_name()
+            for name, v in self._named_variables():
+                if name not in r:
+                    missing.append(name)
+                elif isinstance(v, V.GlobalStep):
+                    v.assign(int(r.get_tensor(name).item()))
                 else:
-                    missing.append(v.name)
-            if "global_step" in r and V.get_global_step() is not None:
+                    v.master.copy_(r.get_tensor(name).to(v.master.dtype).to(v.master.device))
+            if not by_name and "global_step" in r and V.get_global_step() is not None:
                 V.get_global_step().assign(int(r.get_tensor("global_step").item()))
             for op in S.train_ops():
                 if op.reducer is None:
                     continue
                 op.step_count = V.get_global_step().value() if V.get_global_step() is not None else op.step_count
-                for state, suffix in op.optimizer.slot_checkpoint_names():
+                if not by_name and op.ema is not None:
+                    # <var>/ExponentialMovingAverage; a variable whose average the checkpoint lacks (one written
+                    # without averages) starts from its restored weights
+                    fulls = []
+                    for g in op.space.groups:
+                        full = g.master.detach().clone()
+                        for var in g.variables:
+                            key = op.ema.average_name(var)
+                            if key in r:
+                                o = var.flat_offset
+                                full[o:o + var.numel()].copy_(r.get_tensor(key).reshape(-1).to(full.device))
+                        fulls.append(full)
+                    op.ema.load_full(fulls)
+                for state, suffix in (() if by_name else op.optimizer.slot_checkpoint_names()):
                     fulls = []
                     for g in op.space.groups:
                         full = torch.zeros(g.numel, dtype=torch.float32, device=g.device)

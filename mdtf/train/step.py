@@ -394,6 +394,7 @@ class TrainOp(Fetchable):
         self.last_global_norm = None    # device/CPU tensor [norm, coef] of the last step
         self._layer_map = None          # ops.layerwise.LayerMap / LayerBuffers of a layer-wise optimizer (LAMB,
         self._layer_buf = None          # LARS), allocated by the first (eager) step; None for every other one
+        self.ema = None                 # train.moving_averages.ExponentialMovingAverage attached by its apply()
         _register(self)
 
     # -- finalisation: flat buffers + reducer ----------------------------
@@ -442,6 +443,11 @@ class TrainOp(Fetchable):
         from ..ops import conv as _conv
         from ..ops import gemm as _gemm
         red = self.reducer
+        captured = dyn is not None      # the StepGraph's buffer as passed in (a clip rebinds ``dyn`` below)
+        if self.ema is not None:
+            # the averages start as the weights before the first update (raises inside a capture: allocated and
+            # filled by the first eager step, like the norm and layer buffers)
+            self.ema.ensure_initialized()
         red.begin_step()
         lr = self.optimizer.learning_rate(step)
         if red.R == red.world and self.clip is None and not self.optimizer.layerwise:
@@ -476,6 +482,10 @@ class TrainOp(Fetchable):
                 self._layer_map, self._layer_buf = LW.state_for(targets, red)
             self.optimizer.update_all(targets, lr, scale, self.step_count, dyn=dyn, reducer=red)
             red.after_update()
+            if self.ema is not None:
+                # over every target, also those sharded mode updated during backward (update_targets() is
+                # empty then); a captured step reads 1 - decay from the average's device buffer
+                self.ema.update(step, captured=captured)
         return scale
 
     def _clip_dyn(self, targets, lr, scale, dyn):
