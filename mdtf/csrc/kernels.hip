@@ -658,20 +658,60 @@ __global__ void lrn_fwd(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, fl
   }
 }
 
-__global__ void lrn_bwd(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
-                        const float* __restrict__ dsave, bf16_t* __restrict__ dx, long long P, int C, int r,
-                        float alpha, float beta) {
+// dx_c = dy_c d_c^-beta - 2 alpha beta x_c sum_j w_j,  w_j = dy_j y_j / d_j = dy_j x_j d_j^-beta / d_j formed in fp32
+// from x and the saved d: the stored y is rounded to bf16, and where the two terms of dx cancel that rounding came
+// out as several bf16 steps of dx.  A block takes kT consecutive elements and stages w, with dy d^-beta next to it,
+// of those and of the r elements on either side in LDS (one pow and one division per element, not per tap); every
+// thread sums its window from there.  The window is clipped to the thread's own row of C channels, so what was
+// staged from the neighbouring rows is not read.
+constexpr int kLrnMaxR = 64;   // larger radii: lrn_bwd_direct
+
+__global__ void __launch_bounds__(kT) lrn_bwd(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                              const float* __restrict__ dsave, bf16_t* __restrict__ dx, long long P,
+                                              int C, int r, float alpha, float beta) {
+  __shared__ float W[kT + 2 * kLrnMaxR];   // w of elements [b0 - r, b0 + kT + r)
+  __shared__ float A[kT + 2 * kLrnMaxR];   // dy d^-beta of the same elements
+  const long long total = P * C;
+  for (long long b0 = (long long)blockIdx.x * kT; b0 < total; b0 += (long long)gridDim.x * kT) {
+    for (int t = threadIdx.x; t < kT + 2 * r; t += kT) {
+      const long long j = b0 - r + t;
+      float a = 0.f, w = 0.f;
+      if (j >= 0 && j < total) {
+        const float d = dsave[j];
+        a = bf2f(dy[j]) * __powf(d, -beta);
+        w = a * bf2f(x[j]) / d;
+      }
+      A[t] = a;
+      W[t] = w;
+    }
+    __syncthreads();
+    const long long i = b0 + threadIdx.x;
+    if (i < total) {
+      // 32-bit remainder where the index fits: the 64-bit one is a long instruction sequence per element
+      const int c = total <= 0xffffffffLL ? static_cast<int>(static_cast<uint32_t>(i) % static_cast<uint32_t>(C))
+                                          : static_cast<int>(i % C);
+      const int lo = max(0, c - r) - c, hi = min(C - 1, c + r) - c;
+      float t = 0.f;
+      for (int o = lo; o <= hi; ++o) t += W[threadIdx.x + r + o];
+      dx[i] = f2bf(A[threadIdx.x + r] - 2.f * alpha * beta * bf2f(x[i]) * t);
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void lrn_bwd_direct(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                               const float* __restrict__ dsave, bf16_t* __restrict__ dx, long long P, int C, int r,
+                               float alpha, float beta) {
   long long total = P * C;
   GRID_STRIDE(i, total) {
     int c = static_cast<int>(i % C);
     long long base = i - c;
-    float xi = bf2f(x[i]);
-    float acc = bf2f(dy[i]) * __powf(dsave[i], -beta);
     float t = 0.f;
-    for (int j = max(0, c - r); j <= min(C - 1, c + r); ++j)
-      t += bf2f(dy[base + j]) * bf2f(y[base + j]) / dsave[base + j];
-    acc -= 2.f * alpha * beta * xi * t;
-    dx[i] = f2bf(acc);
+    for (int j = max(0, c - r); j <= min(C - 1, c + r); ++j) {
+      const float d = dsave[base + j];
+      t += bf2f(dy[base + j]) * bf2f(x[base + j]) * __powf(d, -beta) / d;
+    }
+    dx[i] = f2bf(bf2f(dy[i]) * __powf(dsave[i], -beta) - 2.f * alpha * beta * bf2f(x[i]) * t);
   }
 }
 
@@ -1070,10 +1110,16 @@ MDTF_EXPORT int mdtf_lrn_fwd(const void* x, void* y, float* dsave, long long P, 
   return 0;
 }
 
-MDTF_EXPORT int mdtf_lrn_bwd(const void* dy, const void* x, const void* y, const float* dsave, void* dx, long long P,
-                             int C, int r, float alpha, float beta, hipStream_t st) {
-  hipLaunchKernelGGL(lrn_bwd, dim3(grid_cap(P * C)), dim3(kT), 0, st, (const bf16_t*)dy, (const bf16_t*)x,
-                     (const bf16_t*)y, dsave, (bf16_t*)dx, P, C, r, alpha, beta);
+// (y, the forward's bf16 output, is not read: see lrn_bwd)
+MDTF_EXPORT int mdtf_lrn_bwd(const void* dy, const void* x, const void* /*y*/, const float* dsave, void* dx,
+                             long long P, int C, int r, float alpha, float beta, hipStream_t st) {
+  if (r < 0) return MDTF_EINVAL;
+  if (r <= kLrnMaxR)
+    hipLaunchKernelGGL(lrn_bwd, dim3(grid_cap(P * C)), dim3(kT), 0, st, (const bf16_t*)dy, (const bf16_t*)x, dsave,
+                       (bf16_t*)dx, P, C, r, alpha, beta);
+  else
+    hipLaunchKernelGGL(lrn_bwd_direct, dim3(grid_cap(P * C)), dim3(kT), 0, st, (const bf16_t*)dy, (const bf16_t*)x,
+                       dsave, (bf16_t*)dx, P, C, r, alpha, beta);
   MDTF_LAUNCH_CHECK();
   return 0;
 }

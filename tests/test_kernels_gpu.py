@@ -957,7 +957,8 @@ def test_colsum_kernel(M, C):
     assert _rel(out.cpu(), ref) < 1e-4
 
 
-@pytest.mark.parametrize("B,R,S", [(2, 72, 200), (1, 4608, 512), (3, 8, 64)])
+# (2,56,72), (2,8,56), (1,72,8): a tile edge that is a multiple of 8 but not of 64, on R, on S and on both
+@pytest.mark.parametrize("B,R,S", [(2, 72, 200), (1, 4608, 512), (3, 8, 64), (2, 56, 72), (2, 8, 56), (1, 72, 8)])
 def test_transpose16(B, R, S):
     from mdtf.ops import kernels
     x = torch.randn(B, R, S).bfloat16()
