@@ -39,6 +39,9 @@ def parse():
                    help="clip the gradient by this global norm (global_clipnorm=; BERT's recipe uses 1.0); 0: off")
     p.add_argument("--optimizer", default="adamw", choices=["adamw", "lamb"],
                    help="adamw: AdamWeightDecayOptimizer (the default); lamb: LAMBOptimizer (per-layer trust ratios)")
+    p.add_argument("--weighted_mlm", action="store_true",
+                   help="variable predictions per example ([B, 2P + 1] ground truth with masked_lm_weights) and the "
+                        "weighted masked-LM loss sum(w l) / (sum(w) + 1e-5) (mdtf.losses)")
     p.add_argument("--trace_ops", default=None,
                    help="after the warm-up, profile one step with Python stacks (use --hip_graph 0) into this dir")
     return p.parse_args()
@@ -151,14 +154,14 @@ def main():
         store = V.get_store()
         store.device = dev
         store.compute_dtype = torch.bfloat16 if gpu else None
-        ld = SyntheticBertLoader(args.seq, P, seed=rank)
+        ld = SyntheticBertLoader(args.seq, P, seed=rank, variable_predictions=args.weighted_mlm)
         ld.batch_size = args.batch
         raw, gt = ld.load_train_batch()
         opt_cls = mdtf.train.LAMBOptimizer if args.optimizer == "lamb" else mdtf.train.AdamWeightDecayOptimizer
         base = opt_cls(1e-4, weight_decay_rate=0.01, global_clipnorm=args.clip_norm if args.clip_norm > 0 else None)
         tg = []
         tower = Tower(Net(Bert(args.size, seq_len=args.seq, max_predictions=P)), "tower_0/", tg, raw, gt,
-                      BertPretrainingLoss(P), base, batch_size=args.batch)
+                      BertPretrainingLoss(P, weighted=args.weighted_mlm), base, batch_size=args.batch)
         _, loss_h, _ = tower.process()
         opt = mdtf.train.SyncReplicasOptimizer(base, world, world, hip_graph=bool(args.hip_graph) and gpu,
                                                mode=args.mode, comm_dtype=args.comm_dtype,

@@ -21,4 +21,5 @@ from .train.step import placeholder, clip_by_global_norm, global_norm  # noqa: F
 from .cluster import ClusterSpec, Server  # noqa: F401
 from . import app  # noqa: F401
 from . import estimator  # noqa: F401
+from . import losses  # noqa: F401
 from . import errors  # noqa: F401

@@ -163,6 +163,8 @@ DEFINE_float('clip_norm', 0.0, "Clip the averaged gradient by this global norm (
              "optimizer sets no global_clipnorm of its own; 0: off.")
 DEFINE_float('moving_average_decay', 0.0, "Keep tf.train.ExponentialMovingAverage(decay, num_updates=global_step) of "
              "the weights while training; Eval then evaluates the averaged weights; 0: off.")
+DEFINE_float('label_smoothing', 0.0, "Label smoothing of models.SoftmaxCrossEntropyLoss when the loss is built without "
+             "an argument (the annotation-configured run loop); 0: off.")
 
 
 def apply_thread_flags():

@@ -174,13 +174,27 @@ class Bert(Model):
 
 
 class BertPretrainingLoss(Loss):
-    """Masked-LM cross entropy + next-sentence cross entropy (fp32)."""
+    """Masked-LM cross entropy + next-sentence cross entropy (fp32).
 
-    def __init__(self, max_predictions=20):
+    ``weighted``: the ground truth is ``[B, 2P + 1]`` -- P ids, the next-sentence label, then P ``masked_lm_weights``
+    (1 for a real prediction, 0 for a padding slot) -- and the masked-LM loss is the recipe's
+    ``sum(w * l) / (sum(w) + 1e-5)``, reduced on the device (``mdtf.losses``)."""
+
+    def __init__(self, max_predictions=20, weighted=False):
         self.P = max_predictions
+        self.weighted = weighted
 
     def loss(self, predict, ground_truth):
         mlm, nsp = predict
+        if self.weighted:
+            from .. import losses
+            P = self.P
+            l1 = losses.sparse_softmax_cross_entropy(ground_truth[:, :P].reshape(-1), mlm.reshape(-1, mlm.shape[-1]),
+                                                     weights=ground_truth[:, P + 1:2 * P + 1].reshape(-1),
+                                                     reduction=losses.Reduction.MEAN, denominator_epsilon=1e-5)
+            l2 = losses.sparse_softmax_cross_entropy(ground_truth[:, P], nsp,
+                                                     reduction=losses.Reduction.SUM_OVER_BATCH_SIZE)
+            return l1 + l2
         lm_ids = ground_truth[:, :self.P].reshape(-1)
         ns = ground_truth[:, self.P]
         l1 = ops.sparse_softmax_cross_entropy_with_logits(lm_ids, mlm.reshape(-1, mlm.shape[-1])).mean()
@@ -192,8 +206,9 @@ class SyntheticBertLoader(object):
     """Synthetic pre-training batches of the packed BERT layout (device resident)."""
     type = "SyntheticDataLoader"
 
-    def __init__(self, seq_len=128, max_predictions=20, vocab=30522, seed=0):
+    def __init__(self, seq_len=128, max_predictions=20, vocab=30522, seed=0, variable_predictions=False):
         self.S, self.P, self.vocab, self.seed = seq_len, max_predictions, vocab, seed
+        self.variable_predictions = variable_predictions     # [B, 2P + 1] ground truth: see BertPretrainingLoss
         self.batch_size = 32
         self._batch = None
 
@@ -206,6 +221,11 @@ class SyntheticBertLoader(object):
         pos = torch.stack([torch.randperm(S_, generator=g)[:P].sort().values for _ in range(B)])
         raw = torch.cat([ids, types, mask, pos], 1)
         gt = torch.cat([torch.randint(0, self.vocab, (B, P), generator=g), torch.randint(0, 2, (B, 1), generator=g)], 1)
+        if self.variable_predictions:
+            # real records fill 1 .. P slots: the unused ones carry id 0 and weight 0
+            count = torch.randint(1, P + 1, (B, 1), generator=g)
+            w = (torch.arange(P).unsqueeze(0) < count).long()
+            gt = torch.cat([gt[:, :P] * w, gt[:, P:], w], 1)
         dev = V.get_store().device
         return raw.to(dev), gt.to(dev)
 

@@ -12,8 +12,7 @@ names follow TF-slim style scopes (``resnet_v1_50/block1/unit_1/conv1/weights``)
 """
 import os
 
-import torch
-
+from ..config.flags import FLAGS
 from ..layers import tools
 from ..ops import nn as ops
 from ..runtime.model import Loss, Model
@@ -100,16 +99,16 @@ class ResNet152(ResNet):
 
 
 class SoftmaxCrossEntropyLoss(Loss):
-    """Mean sparse softmax cross entropy (fp32), optional label smoothing."""
+    """Mean sparse softmax cross entropy (fp32), optional label smoothing (``None``: the ``--label_smoothing``
+    flag; non-zero runs ``mdtf.losses.sparse_softmax_cross_entropy`` on the device)."""
 
-    def __init__(self, label_smoothing=0.0):
-        self.label_smoothing = label_smoothing
+    def __init__(self, label_smoothing=None):
+        self.label_smoothing = float(FLAGS.label_smoothing if label_smoothing is None else label_smoothing)
 
     def loss(self, predict, ground_truth):
         if self.label_smoothing:
-            n = predict.shape[-1]
-            logp = torch.log_softmax(predict.float(), -1)
-            onehot = torch.nn.functional.one_hot(ground_truth.long(), n).float()
-            target = onehot * (1 - self.label_smoothing) + self.label_smoothing / n
-            return -(target * logp).sum(-1).mean()
+            from .. import losses
+            return losses.sparse_softmax_cross_entropy(ground_truth, predict,
+                                                       reduction=losses.Reduction.SUM_OVER_BATCH_SIZE,
+                                                       label_smoothing=self.label_smoothing)
         return ops.sparse_softmax_cross_entropy_with_logits(ground_truth, predict).mean()
