@@ -662,6 +662,7 @@ MDTF_EXPORT int mdtf_ln_fwd(const void* x, const void* res, const float* gamma, 
                             float* mean, float* rstd, long long rows, int H, float eps, float p_drop, unsigned seed,
                             const long long* seed_off, hipStream_t st) {
   if (H % 8) return MDTF_EINVAL;
+  if (rows <= 0) return 0;      // (a grid of 0 blocks is a launch error)
   if (rows * H > 0xffffffffLL && p_drop > 0.f) return MDTF_EUNSUPPORTED;
   const uint32_t thr = drop_thr(p_drop);
   const float inv_keep = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
@@ -705,6 +706,10 @@ static long long ln_bwd_rpb() {
 }
 
 static void ln_bwd_geometry(long long rows, int* blocks, int* rpb) {
+  if (rows <= 0) {      // (no rows: no blocks, no workspace; rows / rpb below would divide by zero)
+    *blocks = *rpb = 0;
+    return;
+  }
   long long b = ceil_div(rows, ln_bwd_rpb());  // >= 4 rows per wave (all in flight together) by default
   const long long cap = ln_bwd_rpb() == 16 ? 512 : 2048;
   if (b > cap) b = cap;
@@ -787,6 +792,7 @@ MDTF_EXPORT int mdtf_ln_bwd(const void* dy, const void* s, const float* gamma, c
 MDTF_EXPORT int mdtf_softmax_fwd(const void* x, const float* mask, void* y, long long rows, int cols, float scale,
                                  long long rows_per_batch, hipStream_t st) {
   if (cols % 8) return MDTF_EINVAL;
+  if (rows <= 0) return 0;
   NV_DISPATCH(cols, softmax_fwd_kernel, dim3(ceil_div(rows, kT / 64)), (const bf16_t*)x, mask, (bf16_t*)y, rows,
               cols, scale, rows_per_batch);
   MDTF_LAUNCH_CHECK();
@@ -796,6 +802,7 @@ MDTF_EXPORT int mdtf_softmax_fwd(const void* x, const float* mask, void* y, long
 MDTF_EXPORT int mdtf_softmax_bwd(const void* dy, const void* y, void* dx, long long rows, int cols, float scale,
                                  hipStream_t st) {
   if (cols % 8) return MDTF_EINVAL;
+  if (rows <= 0) return 0;
   NV_DISPATCH(cols, softmax_bwd_kernel, dim3(ceil_div(rows, kT / 64)), (const bf16_t*)dy, (const bf16_t*)y,
               (bf16_t*)dx, rows, cols, scale);
   MDTF_LAUNCH_CHECK();
