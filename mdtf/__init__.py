@@ -22,4 +22,5 @@ from .cluster import ClusterSpec, Server  # noqa: F401
 from . import app  # noqa: F401
 from . import estimator  # noqa: F401
 from . import losses  # noqa: F401
+from . import metrics  # noqa: F401
 from . import errors  # noqa: F401

@@ -165,6 +165,8 @@ DEFINE_float('moving_average_decay', 0.0, "Keep tf.train.ExponentialMovingAverag
              "the weights while training; Eval then evaluates the averaged weights; 0: off.")
 DEFINE_float('label_smoothing', 0.0, "Label smoothing of models.SoftmaxCrossEntropyLoss when the loss is built without "
              "an argument (the annotation-configured run loop); 0: off.")
+DEFINE_integer('eval_top_k', 5, "Eval also reports top_<k>_accuracy (mdtf.metrics.top_k_accuracy) of a classifier with "
+               "more than k classes; 0: off.")
 
 
 def apply_thread_flags():

@@ -332,6 +332,8 @@ class Estimator(object):
         ckpt = self._restore(checkpoint_path)
         total_loss, n = 0.0, 0
         sums, weights = collections.defaultdict(float), collections.defaultdict(float)
+        from ..metrics import Accumulator, MetricValue
+        streaming = {}                  # MetricValue entries: accumulated on the device, read once after the loop
         while steps is None or n < steps:
             ctx = S.RunContext()
             try:
@@ -340,6 +342,9 @@ class Estimator(object):
                 break
             total_loss += float(out["loss"])
             for k, v in (out.get("metrics") or {}).items():
+                if isinstance(v, MetricValue):
+                    streaming.setdefault(k, Accumulator()).update(v)
+                    continue
                 val, w = (v if isinstance(v, tuple) else (v, 1.0))
                 sums[k] += float(val) * float(w)
                 weights[k] += float(w)
@@ -349,6 +354,8 @@ class Estimator(object):
         res = {"loss": total_loss / max(n, 1), "global_step": V.get_global_step().value()}
         for k in sums:
             res[k] = sums[k] / max(weights[k], 1e-12)
+        for k, acc in streaming.items():
+            res[k] = acc.result()
         logger.info("Saving dict for global step %d: %s" % (res["global_step"], ", ".join(
             "%s = %g" % (k, v) for k, v in sorted(res.items()))))
         out_dir = os.path.join(self._model_dir, "eval" if not name else "eval_" + name)

@@ -201,6 +201,29 @@ class BertPretrainingLoss(Loss):
         l2 = ops.sparse_softmax_cross_entropy_with_logits(ns, nsp).mean()
         return l1 + l2
 
+    def metrics(self, predict, ground_truth):
+        """The recipe's evaluation metrics (``mdtf.metrics``, accumulated on the device by ``Eval``):
+        ``masked_lm_accuracy`` and ``masked_lm_loss`` under the ``masked_lm_weights`` of the weighted layout (a padding
+        slot is skipped: its logits are not read), ``next_sentence_accuracy`` and ``next_sentence_loss``.
+        ``masked_lm_accuracy`` is ``top_k_accuracy(k=1)``: an exact tie of another class with the target's logit still
+        counts as a hit, which TF's ``argmax`` form does not."""
+        from .. import metrics as M
+        from ..ops import losses as L
+        mlm, nsp = predict
+        mlm = mlm.detach().reshape(-1, mlm.shape[-1])
+        nsp = nsp.detach()
+        P = self.P
+        ids, ns = ground_truth[:, :P].reshape(-1), ground_truth[:, P]
+        w = ground_truth[:, P + 1:2 * P + 1].reshape(-1).float() if self.weighted else None
+        with torch.no_grad():
+            live = (w != 0).float() if w is not None else None      # rows of weight 0 stay unread and are exact zeros
+            mlm_rows = L.weighted_softmax_xent(mlm, ids, live, mode=L.NONE)
+            nsp_rows = L.weighted_softmax_xent(nsp, ns, None, mode=L.NONE)
+            return {"masked_lm_accuracy": M.top_k_accuracy(ids, mlm, 1, weights=w),
+                    "masked_lm_loss": M.mean(mlm_rows, weights=w),
+                    "next_sentence_accuracy": M.accuracy(ns, nsp.argmax(-1)),
+                    "next_sentence_loss": M.mean(nsp_rows)}
+
 
 class SyntheticBertLoader(object):
     """Synthetic pre-training batches of the packed BERT layout (device resident)."""

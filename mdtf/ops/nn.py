@@ -408,6 +408,14 @@ def reduce_mean(t, axis=None):
     return t.float().mean() if axis is None else t.float().mean(dim=axis)
 
 
+def in_top_k(predictions, targets, k, name=None):
+    """``tf.nn.in_top_k``: bool [N], whether ``targets`` (int32 / int64, [N] or [N, 1]) are among the top ``k`` of
+    the rows of ``predictions`` [N, K].  Classes tied with the target count as inside the top k; a target outside
+    ``[0, K)`` or with a non-finite prediction is False."""
+    from . import metrics
+    return metrics.in_top_k_hits(predictions, targets, k) != 0
+
+
 def add_n(ts):
     out = ts[0]
     for t in ts[1:]:

@@ -5,8 +5,13 @@ Builds the model forward from ``data_loader.load_eval_batch()`` under the same
 variable names, restores the latest checkpoint from ``model_dir`` (waiting for
 one up to ``checkpoint_wait_secs``), runs ``eval_steps`` batches in inference
 mode (BN uses moving statistics) and reports mean loss and — when the logits
-are class scores and the ground truth integer labels — top-1 accuracy.  Eval
-tasks of a multi-replica job shard the batches and all-reduce the sums.
+are class scores and the ground truth integer labels — top-1 accuracy and
+``top_<k>_accuracy`` (``--eval_top_k``, default 5, for more than k classes),
+plus whatever the ``Loss.metrics`` hook returns, under its names.  Any other
+``logits`` (a tuple, as BERT's) get the loss and the hook's metrics.  All of
+them are ``mdtf.metrics`` accumulated on the device and read once after the
+loop.  Eval tasks of a multi-replica job shard the batches and all-reduce the
+sums; every replica must report the same metric names.
 """
 import time
 
@@ -19,6 +24,23 @@ from ..train import step as S
 from ..train import variables as V
 from ..utils import log as logger
 from .tower import Tower
+
+
+def pack_sums(steps, loss_acc, correct_acc, extras, device):
+    """The fp64 vector a multi-replica Eval all-reduces, built on ``device`` without a host read:
+    ``[loss total, correct, count, steps]`` followed by ``{total, count}`` of every accumulator in ``extras``."""
+    parts = [loss_acc.tensor[:1], correct_acc.tensor, torch.tensor([float(steps)], dtype=torch.float64)]
+    parts += [a.tensor for a in extras]
+    return torch.cat([p.to(device) for p in parts])
+
+
+def unpack_sums(t, names):
+    """``(loss total, correct, count, steps, {name: (total, count)})`` from the vector of :func:`pack_sums`; the
+    one host read of an evaluation."""
+    v = t.tolist()
+    if len(v) != 4 + 2 * len(names):
+        raise ValueError("expected %d sums for %r, got %d" % (4 + 2 * len(names), names, len(v)))
+    return v[0], v[1], v[2], v[3], {n: (v[4 + 2 * i], v[5 + 2 * i]) for i, n in enumerate(names)}
 
 
 class Eval(object):
@@ -50,7 +72,12 @@ class Eval(object):
         else:
             logger.warn("Eval: no checkpoint in %r; evaluating the initial weights" % (self.model_dir,))
         steps = int(getattr(self, "eval_steps", 0) or max(self.sample_number // max(self.batch_size, 1), 1))
-        total_loss, correct, count = 0.0, 0.0, 0.0
+        from .. import metrics as M
+        top_k = getattr(self, "eval_top_k", None)                   # an attribute of 0 switches a set flag off
+        top_k = int((FLAGS.eval_top_k if top_k is None else top_k) or 0)
+        loss_metrics = getattr(self.loss, "metrics", None)
+        # streaming state on the device: nothing is read by the host before the loop ends
+        loss_acc, correct_acc, extra = M.Accumulator(), M.Accumulator(), {}
         sample_queue = None
         if self.input_mode == InputOptions.PLACEHOLDER:
             sample_queue = self.data_loader.load_queue_for_placeholder(self.data_dir)
@@ -64,22 +91,31 @@ class Eval(object):
                 out = tower.program.forward(ctx, grad=False)
             except StopIteration:
                 break
-            lv = out["loss"].detach().float()
             logits = out["logits"]
             labels = tower._ground_truth_value
-            total_loss += float(lv)
-            if logits.dim() == 2 and labels is not None and not labels.is_floating_point() and labels.dim() == 1:
-                correct += float((logits.argmax(-1) == labels.to(logits.device)).sum())
-                count += labels.numel()
+            with torch.no_grad():
+                M.mean(out["loss"].detach().float().reshape(1), accumulator=loss_acc)
+                if (isinstance(logits, torch.Tensor) and logits.dim() == 2 and isinstance(labels, torch.Tensor)
+                        and not labels.is_floating_point() and labels.dim() == 1):
+                    M.accuracy(labels, logits.argmax(-1), accumulator=correct_acc)
+                    if 0 < top_k < logits.shape[1]:
+                        M.top_k_accuracy(labels, logits, top_k,
+                                         accumulator=extra.setdefault("top_%d_accuracy" % top_k, M.Accumulator()))
+                hooked = loss_metrics(logits, labels) if loss_metrics is not None else None
+                for name, mv in (hooked or {}).items():
+                    extra.setdefault(name, M.Accumulator()).update(mv)
+        names = sorted(extra)
+        dev = V.get_store().device if V.get_store().device.type == "cuda" else torch.device("cpu")
+        t = pack_sums(steps, loss_acc, correct_acc, [extra[n] for n in names], dev)
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and server is not None and server.worker_group is not None:
-            t = torch.tensor([total_loss, correct, count, float(steps)], dtype=torch.float64,
-                             device=V.get_store().device if V.get_store().device.type == "cuda" else "cpu")
-            dist.all_reduce(t, group=server.worker_group)
-            total_loss, correct, count, steps = t.tolist()
+            dist.all_reduce(t, group=server.worker_group)           # every replica reports the same names
+        total_loss, correct, count, steps, sums = unpack_sums(t, names)
         self.metrics = {"loss": total_loss / max(steps, 1),
                         "accuracy": (correct / count) if count else None,
                         "global_step": V.get_global_step().value(), "steps": int(steps)}
+        for n in names:
+            self.metrics[n] = (sums[n][0] / sums[n][1]) if sums[n][1] else 0.0
         logger.info("Eval: %s" % self.metrics)
         if server is not None:
             server.signal_done()

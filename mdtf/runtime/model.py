@@ -16,3 +16,8 @@ class Loss(metaclass=abc.ABCMeta):
     @abc.abstractmethod
     def loss(self, predict, ground_truth):
         """Return a scalar loss tensor."""
+
+    def metrics(self, predict, ground_truth):
+        """Evaluation metrics of one batch: ``{name: mdtf.metrics.MetricValue}``, or None for none.  ``Eval`` calls
+        it after every forward and reports each name accumulated over the batches."""
+        return None
