@@ -23,4 +23,5 @@ from . import app  # noqa: F401
 from . import estimator  # noqa: F401
 from . import losses  # noqa: F401
 from . import metrics  # noqa: F401
+from . import image  # noqa: F401
 from . import errors  # noqa: F401

@@ -329,3 +329,22 @@ class SyntheticDataLoader(Dataloader):
 
     def load_eval_batch(self, *args, **kwargs):
         return self.load_train_batch()
+
+
+class SyntheticImageLoader(SyntheticDataLoader):
+    """Device-resident random uint8 images of ``stored_shape`` = (height, width, channels) with int64 labels: the
+    input of a step that preprocesses on the device (``mdtf.image``), as raw image bytes decoded from records are.
+    The batch is generated once and reused every step, like :class:`SyntheticDataLoader`'s."""
+    type = "SyntheticImageLoader"
+
+    def __init__(self, stored_shape=(256, 256, 3), num_classes=1000, seed=0):
+        super(SyntheticImageLoader, self).__init__(shape=stored_shape, num_classes=num_classes, dtype=torch.uint8,
+                                                   seed=seed)
+
+    def _make(self):
+        from ..train import variables as V
+        dev = V.get_store().device
+        g = torch.Generator(device="cpu").manual_seed(self.seed)
+        x = torch.randint(0, 256, (self.batch_size,) + self.shape, generator=g, dtype=torch.uint8)
+        y = torch.randint(0, self.num_classes, (self.batch_size,), generator=g)
+        return x.to(dev), y.to(dev)
