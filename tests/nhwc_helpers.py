@@ -211,6 +211,9 @@ def _taps(geo, h, w, k, s):
                         yield oh, ow, kh, kw, ih, iw
 
 
+taps = _taps                     # public name: bn_helpers walks the windows in the same scan order
+
+
 def pool_ref(x, k, s, padding, is_max):
     """x: fp64 NHWC.  Returns y, the argmax tap kh*KW + kw (first maximum in scan order), the valid-tap count per
     window and sum|x| over each window."""
