@@ -9,6 +9,7 @@ beats MIOpen, with its best tile); ``MDTF_CONV=mdtf|miopen`` forces one
 backend.  Shapes the HIP kernel cannot take (C % 8 != 0, e.g. a 3-channel
 stem) use MIOpen.
 """
+import collections
 import ctypes
 import json
 import os
@@ -134,9 +135,43 @@ def v2_ok(pass_, c, co, stride=(1, 1), taps=1, dil=(1, 1)):
     return False
 
 
+def _default_wgrad_tile(r, co):
+    return (128 if r >= 128 else 64, 128 if co % 128 == 0 else 64)
+
+
+# What choose() returns: named tuples (a choice still compares equal to a bare tuple) that also tell the dispatch:
+#   stat_rows   output rows per M tile, which sets the partial-row count of fused BN statistics (None: STAT_SLOTS)
+#   sink_aware  the data gradient can write into an activation-gradient sink (out / accumulate / bn_stats /
+#               acc_src of mdtf_dgrad) instead of returning a tensor for it
+class Mdtf(collections.namedtuple("Mdtf", "backend bm bn splits ver stages")):
+    """The implicit-GEMM kernels (csrc/conv_igemm.hip): tile, split-K count, kernel version, pipeline stages."""
+    v2 = sink_aware = property(lambda self: self.ver in (2, 3))
+    stat_rows = property(lambda self: self.bm)
+
+
+class Ws(collections.namedtuple("Ws", "backend tile")):
+    """The weight-stationary kernel (csrc/conv_ws.hip), ``tile`` = (tp, nw, cg, d)."""
+    stat_rows, sink_aware = None, True
+
+
+class Pp(collections.namedtuple("Pp", "backend tile")):
+    """The ping-pong core (csrc/gemm_pp.hip mdtf_conv_pp), ``tile`` an index into PP_TILES."""
+    rows = stat_rows = property(lambda self: PP_TILES[self.tile][0])
+    sink_aware = True
+
+
+class Lib(collections.namedtuple("Lib", "backend")):
+    """``stem`` (the few-channel stem kernels), ``winograd`` or ``miopen``."""
+    stat_rows, sink_aware = None, False
+
+
+def _mdtf(tile, splits=0, ver=1, stages=2):
+    return Mdtf("mdtf", tile[0], tile[1], splits, ver, stages)
+
+
 def choose(pass_, x_shape, w_shape, stride, pads, dil):
-    """-> ('mdtf', bm, bn, splits, version, stages), ('ws', (tp, nw, cg, d)) (the weight-stationary
-    kernel, csrc/conv_ws.hip), ('winograd',) or ('miopen',).
+    """-> ``Mdtf('mdtf', bm, bn, splits, ver, stages)``, ``Ws('ws', (tp, nw, cg, d))``, ``Pp('pp', tile)``,
+    ``Lib('stem')``, ``Lib('winograd')`` or ``Lib('miopen')``.
 
     ``MDTF_CONV``: ``auto`` (table, else defaults), ``mdtf`` (v1 kernels),
     ``mdtf2`` (v2 kernels where the channels allow, else v1), ``miopen``.
@@ -147,11 +182,11 @@ def choose(pass_, x_shape, w_shape, stride, pads, dil):
     native_ok = c % 8 == 0 and co % 8 == 0
     if pass_ in ("fwd", "wgrad") and not native_ok and stem_ok(x_shape, w_shape, dil):
         if pass_ == "fwd" or (co == 64 and kh <= 8 and not N.deterministic()):
-            return ("stem",)
+            return Lib("stem")
     if not native_ok or forced == "miopen":
-        return ("miopen",)
+        return Lib("miopen")
     if pass_ in ("fwd", "dgrad") and winograd.enabled() and winograd.eligible(w_shape, stride, pads, dil, c, co):
-        return ("winograd",)                 # the reference's TF_ENABLE_WINOGRAD_NONFUSED toggle
+        return Lib("winograd")               # the reference's TF_ENABLE_WINOGRAD_NONFUSED toggle
     ent = table().get(shape_key(pass_, x_shape, w_shape, stride, pads, dil))
     if ent is None and n != TUNED_BATCH:
         # batch-agnostic lookup: the same conv at the tuned batch (ResNet-50/101/152 share their conv
@@ -160,31 +195,27 @@ def choose(pass_, x_shape, w_shape, stride, pads, dil):
     if N.deterministic() and pass_ == "wgrad":
         # no split-K atomics, no library algorithm choice: one block per DW tile
         ver = 2 if v2_ok(pass_, c, co, stride, kh * kw, dil) else 1
-        return ("mdtf", 128 if kh * kw * ci >= 128 else 64, 128 if co % 128 == 0 else 64, 1, ver, 2)
+        return _mdtf(_default_wgrad_tile(kh * kw * ci, co), 1, ver)
     if forced == "auto" and ent is not None:
         if ent["backend"] in ("miopen", "winograd"):
-            return (ent["backend"],)
+            return Lib(ent["backend"])
         if ent.get("ver") == 5:                  # ping-pong core (csrc/gemm_pp.hip mdtf_conv_pp)
             if pp_ok(pass_, c, co, stride, kh, kw, ent["tile"]):
-                return ("pp", ent["tile"])
+                return Pp("pp", ent["tile"])
             ent = ent.get("prev")
             if ent is None:
-                return ("mdtf",) + _default_tile(co if pass_ == "fwd" else ci) + (0, 2, 2)
+                return _mdtf(_default_tile(co if pass_ == "fwd" else ci), 0, 2)
             if ent["backend"] in ("miopen", "winograd"):
-                return (ent["backend"],)
+                return Lib(ent["backend"])
         if ent.get("ver") == 4:
             if N.deterministic():                # cross-block statistics atomics: use the v2 kernels
-                return ("mdtf", 128, 128 if (co if pass_ == "fwd" else c) % 128 == 0 else 64, 0, 2, 2)
-            return ("ws", tuple(ent["ws"]))
-        return ("mdtf", ent["bm"], ent["bn"], ent.get("splits", 0), ent.get("ver", 1), ent.get("stages", 2))
-    if pass_ == "wgrad":
-        r = kh * kw * ci
-        ver = 2 if (forced in ("auto", "mdtf2") and v2_ok(pass_, c, co, stride, kh * kw, dil)) else 1
-        return ("mdtf", 128 if r >= 128 else 64, 128 if co % 128 == 0 else 64, 0, ver, 2)
-    ncol = co if pass_ == "fwd" else ci
-    bm, bn = _default_tile(ncol)
+                return _mdtf(_default_tile(co if pass_ == "fwd" else c), 0, 2)
+            return Ws("ws", tuple(ent["ws"]))            # (the only place: never in deterministic mode)
+        return Mdtf("mdtf", ent["bm"], ent["bn"], ent.get("splits", 0), ent.get("ver", 1), ent.get("stages", 2))
     ver = 2 if (forced in ("auto", "mdtf2") and v2_ok(pass_, c, co, stride, kh * kw, dil)) else 1
-    return ("mdtf", bm, bn, 0, ver, 3 if ver == 2 else 2)
+    if pass_ == "wgrad":
+        return _mdtf(_default_wgrad_tile(kh * kw * ci, co), 0, ver)
+    return _mdtf(_default_tile(co if pass_ == "fwd" else ci), 0, ver, 3 if ver == 2 else 2)
 
 
 # ---------------------------------------------------------------------------
@@ -238,10 +269,25 @@ def miopen_bwd(x, w, dy, stride, pads, dil, need_dx, need_dw):
 # ---------------------------------------------------------------------------
 # hand-written kernels
 # ---------------------------------------------------------------------------
-def _geo(x, w, out_hw, stride, pads, dil):
-    n, h, wd, c = x.shape
-    kh, kw, ci, co = w.shape
+def _geo(x_shape, w_shape, out_hw, stride, pads, dil):
+    """The geometry integers of the C ABI; a data gradient passes the shape of DX and the size of DY."""
+    n, h, wd, c = x_shape
+    kh, kw, ci, co = w_shape
     return [n, h, wd, c, out_hw[0], out_hw[1], co, kh, kw, stride[0], stride[1], pads[0], pads[2], dil[0], dil[1]]
+
+
+def _stat_args(stats):
+    """``stats = (psum, psq)`` or None -> (psum, psq, slots)."""
+    s_sum, s_sq = stats if stats is not None else (None, None)
+    return s_sum, s_sq, s_sum.shape[0] if s_sum is not None else 0
+
+
+def _bn_args(bn_stats):                  # (x, relu_mask or None, psum, psq, slots) or None -> five values
+    return bn_stats if bn_stats is not None else (None, None, None, None, 0)
+
+
+def _acc_args(acc_src):                  # (g, relu_mask) or None -> two values
+    return acc_src if acc_src is not None else (None, None)
 
 
 def transpose_filter(w):
@@ -360,19 +406,16 @@ def mdtf_fwd(x, w, out_hw, stride, pads, dil, bm, bn, stats=None, ver=1, stages=
     co = w.shape[3]
     y = torch.empty((n, out_hw[0], out_hw[1], co), dtype=x.dtype, device=x.device)
     mt = N.I(0)
-    s_sum, s_sq = (stats if stats is not None else (None, None))
-    slots = s_sum.shape[0] if s_sum is not None else 0
-    import ctypes
+    s_sum, s_sq, slots = _stat_args(stats)
+    geo = _geo(x.shape, w.shape, out_hw, stride, pads, dil)
     if ver in (2, 3):
         wt = transpose_filter(w)
-        N.check(N.fn("mdtf_conv_fwd_v2")(N.ptr(x), N.ptr(wt), N.ptr(y), N.ptr(s_sum), N.ptr(s_sq), slots,
-                                         *_geo(x, w, out_hw, stride, pads, dil), _v2_code(bm, stages, ver), bn,
-                                         ctypes.byref(mt),
-                                         N.stream_ptr()), "conv_fwd_v2")
+        N.check(N.fn("mdtf_conv_fwd_v2")(N.ptr(x), N.ptr(wt), N.ptr(y), N.ptr(s_sum), N.ptr(s_sq), slots, *geo,
+                                         _v2_code(bm, stages, ver), bn, ctypes.byref(mt), N.stream_ptr()),
+                "conv_fwd_v2")
         return y
-    N.check(N.fn("mdtf_conv_fwd")(N.ptr(x), N.ptr(w), N.ptr(y), N.ptr(s_sum), N.ptr(s_sq), slots,
-                                  *_geo(x, w, out_hw, stride, pads, dil), bm, bn, ctypes.byref(mt), N.stream_ptr()),
-            "conv_fwd")
+    N.check(N.fn("mdtf_conv_fwd")(N.ptr(x), N.ptr(w), N.ptr(y), N.ptr(s_sum), N.ptr(s_sq), slots, *geo, bm, bn,
+                                  ctypes.byref(mt), N.stream_ptr()), "conv_fwd")
     return y
 
 
@@ -385,12 +428,10 @@ def mdtf_dgrad(dy, w, x_shape, stride, pads, dil, bm, bn, ver=1, stages=2, out=N
     ``acc_src = (g, relu_mask)``: accumulate ``g * mask`` instead of ``out``'s contents (a pending
     masked contribution of an activation-gradient sink, ``actsink``)."""
     dx = out if out is not None else torch.empty(x_shape, dtype=dy.dtype, device=dy.device)
-    n, h, wd, c = x_shape
-    kh, kw, ci, co = w.shape
-    geo = [n, h, wd, c, dy.shape[1], dy.shape[2], co, kh, kw, stride[0], stride[1], pads[0], pads[2], dil[0], dil[1]]
+    geo = _geo(x_shape, w.shape, dy.shape[1:3], stride, pads, dil)
     if ver in (2, 3):
-        bx, bmask, bsum, bsq, bslots = bn_stats if bn_stats is not None else (None, None, None, None, 0)
-        ag, am = acc_src if acc_src is not None else (None, None)
+        bx, bmask, bsum, bsq, bslots = _bn_args(bn_stats)
+        ag, am = _acc_args(acc_src)
         N.check(N.fn("mdtf_conv_dgrad_v2")(N.ptr(dy), N.ptr(w), N.ptr(dx), *geo, _v2_code(bm, stages, ver), bn,
                                            int(bool(accumulate) or acc_src is not None), N.ptr(bx), N.ptr(bmask),
                                            N.ptr(bsum), N.ptr(bsq), int(bslots), N.ptr(ag), N.ptr(am),
@@ -485,8 +526,7 @@ def stem_fwd(x, w, out_hw, stride, pads, stats=None, tile=None, keep_x4=None):
                                     N.ptr(w if _STEM_PACK_W else None), N.ptr(wt), kh, kw, co, khp,
                                     N.stream_ptr()), "stem_pack4")
     y = torch.empty((n, out_hw[0], out_hw[1], co), dtype=x.dtype, device=x.device)
-    s_sum, s_sq = stats if stats is not None else (None, None)
-    slots = s_sum.shape[0] if s_sum is not None else 0
+    s_sum, s_sq, slots = _stat_args(stats)
     if STEM_KERNEL == "rows" and tile is None and out_hw[1] <= 128:
         N.check(N.fn("mdtf_stem_conv_rows")(N.ptr(x4), N.ptr(wt), N.ptr(y), n, h4, w4, out_hw[0], out_hw[1], co, kh,
                                             khp, stride[0], stride[1], N.ptr(s_sum), N.ptr(s_sq), slots,
@@ -537,8 +577,7 @@ def ws_fwd(x, wt, kh, kw, out_hw, stride, pads, dil, tile, stats=None, grid_cap=
     n, h, wd, c = x.shape
     co = wt.shape[0]
     y = out if out is not None else torch.empty((n, out_hw[0], out_hw[1], co), dtype=x.dtype, device=x.device)
-    s_sum, s_sq = stats if stats is not None else (None, None)
-    slots = s_sum.shape[0] if s_sum is not None else 0
+    s_sum, s_sq, slots = _stat_args(stats)
     if rows_ok((h, wd), c, co, kh, kw, stride, pads, dil) and tuple(out_hw) == (h, wd):
         N.check(N.fn("mdtf_conv3_rows")(N.ptr(x), N.ptr(wt), N.ptr(y), n, h, wd, 0, N.ptr(s_sum), N.ptr(s_sq), slots,
                                         N.ptr(None), N.ptr(None), N.stream_ptr()), "conv3_rows_fwd")
@@ -558,8 +597,8 @@ def bna_ok(ch, x_shape, w_shape, stride, pads, dil):
     """The forward of this conv can apply a pending BN + ReLU to its operand (``ops.bn`` ON_CONSUMER): the
     weight-stationary kernel on a 1x1 / stride-1 / unpadded conv with 64, 96 or 128 input channels."""
     kh, kw, ci, co = w_shape
-    return (ch[0] == "ws" and kh == 1 and kw == 1 and tuple(stride) == (1, 1) and tuple(pads) == (0, 0, 0, 0)
-            and tuple(dil) == (1, 1) and ci in (64, 96, 128) and ws_depth_ok(ci, ch[1][3] if len(ch[1]) > 3 else 4))
+    return (ch.backend == "ws" and kh == 1 and kw == 1 and tuple(stride) == (1, 1) and tuple(pads) == (0, 0, 0, 0)
+            and tuple(dil) == (1, 1) and ci in (64, 96, 128) and ws_depth_ok(ci, ch.tile[3] if len(ch.tile) > 3 else 4))
 
 
 def ws_fwd_bna(x, wt, tile, stats, pend):
@@ -576,6 +615,11 @@ def ws_fwd_bna(x, wt, tile, stats, pend):
     return y
 
 
+def _ws_stats_tile(tile, bn_stats):
+    """``tp`` is 2 when BN backward statistics ride along (the statistics epilogue's register budget)."""
+    return tile if bn_stats is None else (2,) + tuple(tile[1:])
+
+
 def ws_dgrad(dy, w, x_shape, pads, dil, tile, out=None, accumulate=False, bn_stats=None, grid_cap=0, acc_src=None):
     """DX of a stride-1 conv on the weight-stationary kernel (the filter used flipped, HWIO as is).
     ``bn_stats = (x, relu_mask or None, psum, psq, slots)`` and ``acc_src`` as in :func:`mdtf_dgrad`."""
@@ -584,7 +628,8 @@ def ws_dgrad(dy, w, x_shape, pads, dil, tile, out=None, accumulate=False, bn_sta
     dx = out if out is not None else torch.empty(x_shape, dtype=dy.dtype, device=dy.device)
     ph = (kh - 1) * dil[0] - pads[0]
     pw = (kw - 1) * dil[1] - pads[2]
-    bx, bmask, bsum, bsq, bslots = bn_stats if bn_stats is not None else (None, None, None, None, 0)
+    bx, bmask, bsum, bsq, bslots = _bn_args(bn_stats)
+    ag, am = _acc_args(acc_src)
     if (not accumulate and acc_src is None and rows_ok((h, wd), co, ci, kh, kw, (1, 1), pads, dil)
             and tuple(dy.shape[1:3]) == (h, wd)):
         N.check(N.fn("mdtf_conv3_rows")(N.ptr(dy), N.ptr(w), N.ptr(dx), n, h, wd, 1, N.ptr(bsum), N.ptr(bsq),
@@ -593,9 +638,8 @@ def ws_dgrad(dy, w, x_shape, pads, dil, tile, out=None, accumulate=False, bn_sta
     N.check(N.fn("mdtf_conv_ws")(N.ptr(dy), N.ptr(w), N.ptr(dx), n, dy.shape[1], dy.shape[2], co, h, wd, ci, kh, kw,
                                  1, 1, ph, pw, dil[0], dil[1], 1, _ws_code(*tile), int(grid_cap), N.ptr(None),
                                  N.ptr(None), 0, N.ptr(bx), N.ptr(bmask), N.ptr(bsum), N.ptr(bsq), int(bslots),
-                                 int(bool(accumulate) or acc_src is not None),
-                                 N.ptr(acc_src[0] if acc_src is not None else None),
-                                 N.ptr(acc_src[1] if acc_src is not None else None), N.stream_ptr()), "conv_ws_dgrad")
+                                 int(bool(accumulate) or acc_src is not None), N.ptr(ag), N.ptr(am),
+                                 N.stream_ptr()), "conv_ws_dgrad")
     return dx
 
 
@@ -630,10 +674,8 @@ def ws_dual(dy, w, pconv, x_shape, tile=None, bn_stats=None):
     n, h, wd, c = x_shape
     dy2, w2, s2 = pconv[:3]
     dx = torch.empty(x_shape, dtype=dy.dtype, device=dy.device)
-    bx, bmask, bsum, bsq, bslots = bn_stats if bn_stats is not None else (None, None, None, None, 0)
-    tp, nw, cg = tile or DUAL_TILE
-    if bn_stats is not None and tp > 2:
-        tp = 2                                   # the BN-statistics epilogue's register budget
+    bx, bmask, bsum, bsq, bslots = _bn_args(bn_stats)
+    tp, nw, cg = _ws_stats_tile(tile or DUAL_TILE, bn_stats)
     N.check(N.fn("mdtf_conv_ws_dual")(N.ptr(dy), N.ptr(w), N.ptr(dy2), N.ptr(w2), N.ptr(dx), n, h, wd, c,
                                       w.shape[3], dy2.shape[1], dy2.shape[2], dy2.shape[3], s2[0],
                                       _ws_code(tp, nw, cg), N.ptr(bx), N.ptr(bmask), N.ptr(bsum), N.ptr(bsq),
@@ -661,22 +703,20 @@ def pp_fwd(x, w, out_hw, stride, pads, dil, tile, stats=None, out=None):
     n = x.shape[0]
     co = w.shape[3]
     y = out if out is not None else torch.empty((n, out_hw[0], out_hw[1], co), dtype=x.dtype, device=x.device)
-    s_sum, s_sq = stats if stats is not None else (None, None)
-    slots = s_sum.shape[0] if s_sum is not None else 0
-    N.check(N.fn("mdtf_conv_pp")(1, N.ptr(x), N.ptr(transpose_filter(w)), N.ptr(y), *_geo(x, w, out_hw, stride, pads, dil),
-                                 int(tile), N.ptr(s_sum), N.ptr(s_sq), slots, 0, None, None, None, None, None, None, 0,
-                                 N.stream_ptr()), "conv_pp_fwd")
+    s_sum, s_sq, slots = _stat_args(stats)
+    N.check(N.fn("mdtf_conv_pp")(1, N.ptr(x), N.ptr(transpose_filter(w)), N.ptr(y),
+                                 *_geo(x.shape, w.shape, out_hw, stride, pads, dil), int(tile), N.ptr(s_sum),
+                                 N.ptr(s_sq), slots, 0, None, None, None, None, None, None, 0, N.stream_ptr()),
+            "conv_pp_fwd")
     return y
 
 
 def pp_dgrad(dy, w, x_shape, pads, dil, tile, out=None, accumulate=False, bn_stats=None, acc_src=None):
     """DX of a stride-1 conv on the ping-pong core; ``bn_stats`` / ``acc_src`` as in :func:`mdtf_dgrad`."""
     dx = out if out is not None else torch.empty(x_shape, dtype=dy.dtype, device=dy.device)
-    n, h, wd, c = x_shape
-    kh, kw, ci, co = w.shape
-    geo = [n, h, wd, c, dy.shape[1], dy.shape[2], co, kh, kw, 1, 1, pads[0], pads[2], dil[0], dil[1]]
-    bx, bmask, bsum, bsq, bslots = bn_stats if bn_stats is not None else (None, None, None, None, 0)
-    ag, am = acc_src if acc_src is not None else (None, None)
+    geo = _geo(x_shape, w.shape, dy.shape[1:3], (1, 1), pads, dil)
+    bx, bmask, bsum, bsq, bslots = _bn_args(bn_stats)
+    ag, am = _acc_args(acc_src)
     N.check(N.fn("mdtf_conv_pp")(2, N.ptr(dy), N.ptr(w), N.ptr(dx), *geo, int(tile), None, None, 0,
                                  int(bool(accumulate) or acc_src is not None), N.ptr(ag), N.ptr(am), N.ptr(bx),
                                  N.ptr(bmask), N.ptr(bsum), N.ptr(bsq), int(bslots), N.stream_ptr()), "conv_pp_dgrad")
@@ -731,11 +771,6 @@ def mdtf_wgrad(x, dy, w_shape, stride, pads, dil, bm, bn, splits, out=None, ver=
                                     kw, stride[0], stride[1], pads[0], pads[2], dil[0], dil[1], bm, bn, int(splits),
                                     N.stream_ptr()), "conv_wgrad")
     return dw
-
-
-def _pads_ok(pads):
-    # the kernels take (top, left) padding; bottom/right are implied by the output size
-    return True
 
 
 BWD_STATS = os.environ.get("MDTF_BN_BWD_STATS", "1") != "0"   # BN backward statistics from the dgrad epilogue
@@ -862,6 +897,83 @@ def bwd_stats_release(buf, zeroed):
     _BSTATS.setdefault((buf.device, buf.shape[2], buf.shape[1]), []).append(buf)
 
 
+def _fwd_stats(ch, want_stats, rows, co, device):
+    """``(psum, psq)`` for a forward's statistics epilogue, or None.  ``want_stats`` 2: a private zeroed buffer
+    (consumed later than the next conv, e.g. a deferred shortcut BN), else the persistent per-device one."""
+    if not want_stats or ch.backend in ("winograd", "miopen"):
+        return None
+    slots = STAT_SLOTS if ch.stat_rows is None else stat_slots(-(-rows // ch.stat_rows))
+    buf = (torch.zeros((2, slots, co), dtype=torch.float32, device=device) if want_stats == 2
+           else _stats_buffer(co, device, slots))
+    return buf[0], buf[1]
+
+
+def _bwd_stats(xs, stat_rows, x):
+    """``(bn_stats, sbuf)`` when the next contribution to the sink ``xs`` of ``x`` completes the gradient of a BN
+    output that asked for backward statistics (the dgrad epilogue emits them into ``sbuf``), else (None, None).
+    Not in deterministic mode (cross-block atomics), where choose() never returns the ws kernel either."""
+    if xs.stat_req is None or not xs.completing() or not BWD_STATS or N.deterministic():
+        return None, None
+    bx, bmask = xs.stat_req[:2]
+    slots = STAT_SLOTS if stat_rows is None else stat_slots(-(-(x.numel() // x.shape[3]) // stat_rows))
+    sbuf = bwd_stats_acquire(x.device, x.shape[3], slots)
+    return (bx, bmask, sbuf[0], sbuf[1], sbuf.shape[1]), sbuf
+
+
+def _launch_fwd(ch, x, w, out_hw, stride, pads, dil, stats, pend, keep_x4=None):
+    """``pend``: the pending BN apply of ``x`` (``bna_ok`` choices); ``keep_x4`` receives the stem's packed image."""
+    if ch.backend == "mdtf":
+        return mdtf_fwd(x, w, out_hw, stride, pads, dil, ch.bm, ch.bn, stats, ch.ver, ch.stages)
+    if ch.backend == "pp":
+        return pp_fwd(x, w, out_hw, stride, pads, dil, ch.tile, stats)
+    if ch.backend == "stem":
+        return stem_fwd(x, w, out_hw, stride, pads, stats, keep_x4=keep_x4)
+    if ch.backend == "ws":
+        if pend is not None:
+            from . import bn as _bn
+            _bn.ON_CONSUMER_USED[0] += 1
+            return ws_fwd_bna(x, transpose_filter(w), ch.tile, stats, pend)
+        return ws_fwd(x, transpose_filter(w), w.shape[0], w.shape[1], out_hw, stride, pads, dil, ch.tile, stats)
+    if ch.backend == "winograd":
+        return winograd.winograd_fwd(x, w, out_hw, pads)
+    return miopen_fwd(x, w, stride, pads, dil)
+
+
+def _launch_dgrad(cd, dy, w, x_shape, stride, pads, dil, out=None, accumulate=False, bn_stats=None, acc_src=None):
+    """DX on any backend but the library's (``miopen_bwd``); the keywords (:func:`mdtf_dgrad`) need ``sink_aware``."""
+    sink = dict(out=out, accumulate=accumulate, bn_stats=bn_stats, acc_src=acc_src)
+    if cd.backend == "mdtf":
+        return mdtf_dgrad(dy, w, x_shape, stride, pads, dil, cd.bm, cd.bn, cd.ver, cd.stages, **sink)
+    if cd.backend == "pp":
+        return pp_dgrad(dy, w, x_shape, pads, dil, cd.tile, **sink)
+    if cd.backend == "ws":
+        return ws_dgrad(dy, w, x_shape, pads, dil, _ws_stats_tile(cd.tile, bn_stats), **sink)
+    assert cd.backend == "winograd" and out is None and bn_stats is None and acc_src is None, cd
+    return winograd.winograd_dgrad(dy, w, x_shape, pads)
+
+
+def _dgrad_into_sink(xs, cd, dy, w, x, stride, pads, dil, pconv=None):
+    """The data gradient written into the sink ``xs`` of ``x`` (``pconv``: fused with that deferred projection),
+    with BN backward statistics when due.  Returns a BN finalize for this conv's weight-gradient launch or None."""
+    if pconv is None:
+        buf, acc, pend = xs.target_ex()
+        bst, sbuf = _bwd_stats(xs, cd.stat_rows, x)
+        dx = _launch_dgrad(cd, dy, w, x.shape, stride, pads, dil, out=buf, accumulate=acc, bn_stats=bst,
+                           acc_src=pend)
+    else:
+        bst, sbuf = _bwd_stats(xs, None, x)
+        dx = ws_dual(dy, w, pconv, x.shape, bn_stats=bst)
+    xs.written(dx)
+    if bst is None:
+        return None
+    xs.stats = sbuf
+    return _early_finalize(xs, sbuf)
+
+
+def _launch_wgrad(cw, x, dy, w_shape, stride, pads, dil, **kw):
+    return mdtf_wgrad(x, dy, w_shape, stride, pads, dil, cw.bm, cw.bn, cw.splits, ver=cw.ver, stages=cw.stages, **kw)
+
+
 class _Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stride, pads, dil, out_hw, want_stats):
@@ -878,57 +990,19 @@ class _Conv(torch.autograd.Function):
         if pend is not None and not (want_stats and bna_ok(ch, x.shape, w.shape, stride, pads, dil)):
             _bn.apply_pending(pend)
             pend = None
-        stats = None
-        # want_stats 2: a private zeroed partial buffer (statistics consumed later than the next conv, e.g. a
-        # deferred shortcut BN), else the persistent per-device one
-        sbuf = _stats_buffer if want_stats != 2 else (
-            lambda co, dev, slots=STAT_SLOTS: torch.zeros((2, slots, co), dtype=torch.float32, device=dev))
-        if ch[0] == "mdtf":
-            if want_stats:
-                co = w.shape[3]
-                slots = stat_slots(-(-x.shape[0] * out_hw[0] * out_hw[1] // ch[1]))
-                buf = sbuf(co, x.device, slots)
-                stats = (buf[0], buf[1])
-            y = mdtf_fwd(x, w, out_hw, stride, pads, dil, ch[1], ch[2], stats, ch[4], ch[5])
-        elif ch[0] == "pp":
-            if want_stats:
-                co = w.shape[3]
-                slots = stat_slots(-(-x.shape[0] * out_hw[0] * out_hw[1] // PP_TILES[ch[1]][0]))
-                buf = sbuf(co, x.device, slots)
-                stats = (buf[0], buf[1])
-            y = pp_fwd(x, w, out_hw, stride, pads, dil, ch[1], stats)
-        elif ch[0] == "stem":
-            if want_stats:
-                buf = sbuf(w.shape[3], x.device, STAT_SLOTS)
-                stats = (buf[0], buf[1])
-            keep = []
-            y = stem_fwd(x, w, out_hw, stride, pads, stats, keep_x4=keep)
-            ctx.stem_x4 = keep[0]
-        elif ch[0] == "ws":
-            if want_stats:
-                buf = sbuf(w.shape[3], x.device, STAT_SLOTS)
-                stats = (buf[0], buf[1])
-            if pend is not None:
-                y = ws_fwd_bna(x, transpose_filter(w), ch[1], stats, pend)
-                _bn.ON_CONSUMER_USED[0] += 1
-            else:
-                y = ws_fwd(x, transpose_filter(w), w.shape[0], w.shape[1], out_hw, stride, pads, dil, ch[1], stats)
-        elif ch[0] == "winograd":
-            y = winograd.winograd_fwd(x, w, out_hw, pads)
-        else:
-            y = miopen_fwd(x, w, stride, pads, dil)
+        stats = _fwd_stats(ch, want_stats, x.shape[0] * out_hw[0] * out_hw[1], w.shape[3], x.device)
+        keep = []
+        y = _launch_fwd(ch, x, w, out_hw, stride, pads, dil, stats, pend, keep_x4=keep)
+        ctx.stem_x4 = keep[0] if keep else None      # the stem weight gradient reads the packed image again
         ctx.save_for_backward(x, w)
         ctx.args = (stride, pads, dil)
         ctx.w_dtype = w.dtype
         ctx.sink = V.grad_sink(w)
-        if want_stats:
-            if stats is None:
-                empty = torch.empty(0, device=x.device)
-                ctx.mark_non_differentiable(empty, empty)
-                return y, empty, empty
-            ctx.mark_non_differentiable(stats[0], stats[1])
-            return y, stats[0], stats[1]
-        return y
+        if not want_stats:
+            return y
+        psum, psq = stats if stats is not None else (torch.empty(0, device=x.device),) * 2
+        ctx.mark_non_differentiable(psum, psq)
+        return y, psum, psq
 
     @staticmethod
     def backward(ctx, dy, *unused):
@@ -942,138 +1016,63 @@ class _Conv(torch.autograd.Function):
         dx = dw = None
         cd = choose("dgrad", x.shape, w.shape, stride, pads, dil) if need_dx else None
         cw = choose("wgrad", x.shape, w.shape, stride, pads, dil) if need_dw else None
-        if need_dw and cw[0] == "stem" and getattr(ctx, "stem_x4", None) is None:
-            cw = ("miopen",)                   # the forward did not leave the packed image
-        lib_dx = need_dx and cd[0] in ("miopen", "stem")
-        lib_dw = need_dw and cw[0] == "miopen"
+        if need_dw and cw.backend == "stem" and ctx.stem_x4 is None:
+            cw = Lib("miopen")                 # the forward did not leave the packed image
+        lib_dx = need_dx and cd.backend == "miopen"
+        lib_dw = need_dw and cw.backend == "miopen"
         sink = ctx.sink
         if lib_dx or lib_dw:
-            ldx, ldw = miopen_bwd(x, w, dy, stride, pads, dil, lib_dx, lib_dw)
-            if lib_dx:
-                dx = ldx
-            if lib_dw:
-                if sink is not None:
-                    sink.grad.add_(ldw)            # straight into the fp32 grad slot
-                    dw = V.grad_marker(w)
-                else:
-                    dw = ldw
-        xs = ctx.x_sink if need_dx else None
-        if (xs is not None and not lib_dx and xs.idle() and not xs.completing()
-                and proj_deferrable(w.shape, stride, pads, dil) and cd[0] in ("mdtf", "pp")
-                and (cd[0] == "pp" or cd[4] in (2, 3))):
-            # strided 1x1 projection, first contributor: leave its data gradient to the block's 1x1 conv
-            def _run(out, acc, dy=dy, w=w, xshape=tuple(x.shape), stride=stride, pads=pads, dil=dil, cd=cd):
-                if cd[0] == "pp":
-                    return pp_dgrad(dy, w, xshape, pads, dil, cd[1], out=out, accumulate=acc)
-                return mdtf_dgrad(dy, w, xshape, stride, pads, dil, cd[1], cd[2], cd[4], cd[5], out=out,
-                                  accumulate=acc)
-            xs.defer_conv(dy, w, tuple(stride), _run)
-            need_dx = False
-        elif xs is not None and not lib_dx and dual_ok(x.shape, w.shape, stride, pads, dil, xs.pconv) \
-                and xs.buf is None and xs.pend is None:
-            pc = xs.take_conv()
-            bst = None
-            if xs.stat_req is not None and xs.completing() and BWD_STATS and not N.deterministic():
-                bx, bmask = xs.stat_req[:2]
-                sbuf = bwd_stats_acquire(x.device, x.shape[3], STAT_SLOTS)
-                bst = (bx, bmask, sbuf[0], sbuf[1], sbuf.shape[1])
-            xs.written(ws_dual(dy, w, pc, x.shape, bn_stats=bst))
-            if bst is not None:
-                xs.stats = sbuf
-                fin_job = _early_finalize(xs, sbuf)
-            DUAL_FUSED[0] += 1
-            need_dx = False
-        if need_dx and cd[0] == "winograd":
-            dx = winograd.winograd_dgrad(dy, w, x.shape, pads)
-        elif need_dx and cd[0] == "ws":
-            tile = cd[1]
-            if xs is not None:
-                buf, acc, pend = xs.target_ex()
-                bst = None
-                if xs.stat_req is not None and xs.completing() and BWD_STATS:
-                    bx, bmask = xs.stat_req[:2]
-                    sbuf = bwd_stats_acquire(x.device, x.shape[3], STAT_SLOTS)
-                    bst = (bx, bmask, sbuf[0], sbuf[1], sbuf.shape[1])
-                    tile = (2,) + tuple(tile[1:])      # the statistics epilogue's register budget
-                xs.written(ws_dgrad(dy, w, x.shape, pads, dil, tile, out=buf, accumulate=acc, bn_stats=bst,
-                                    acc_src=pend))
-                if bst is not None:
-                    xs.stats = sbuf
-                    fin_job = _early_finalize(xs, sbuf)
-            else:
-                dx = ws_dgrad(dy, w, x.shape, pads, dil, tile)
-        elif need_dx and cd[0] == "pp":
-            if xs is not None:
-                buf, acc, pend = xs.target_ex()
-                bst = None
-                if xs.stat_req is not None and xs.completing() and BWD_STATS and not N.deterministic():
-                    bx, bmask = xs.stat_req[:2]
-                    sbuf = bwd_stats_acquire(x.device, x.shape[3],
-                                             stat_slots(-(-x.numel() // x.shape[3] // PP_TILES[cd[1]][0])))
-                    bst = (bx, bmask, sbuf[0], sbuf[1], sbuf.shape[1])
-                xs.written(pp_dgrad(dy, w, x.shape, pads, dil, cd[1], out=buf, accumulate=acc, bn_stats=bst,
-                                    acc_src=pend))
-                if bst is not None:
-                    xs.stats = sbuf
-                    fin_job = _early_finalize(xs, sbuf)
-            else:
-                dx = pp_dgrad(dy, w, x.shape, pads, dil, cd[1])
-        elif need_dx and not lib_dx:
-            if xs is not None and cd[4] in (2, 3):
-                buf, acc, pend = xs.target_ex()
-                bst = None
-                if xs.stat_req is not None and xs.completing() and BWD_STATS and not N.deterministic():
-                    # this dgrad completes the BN output's gradient: emit the BN backward statistics
-                    bx, bmask = xs.stat_req[:2]
-                    sbuf = bwd_stats_acquire(x.device, x.shape[3], stat_slots(-(-x.numel() // x.shape[3] // cd[1])))
-                    bst = (bx, bmask, sbuf[0], sbuf[1], sbuf.shape[1])
-                xs.written(mdtf_dgrad(dy, w, x.shape, stride, pads, dil, cd[1], cd[2], cd[4], cd[5], out=buf,
-                                      accumulate=acc, bn_stats=bst, acc_src=pend))
-                if bst is not None:
-                    xs.stats = sbuf
-                    fin_job = _early_finalize(xs, sbuf)
-                dx = None
-            else:
-                dx = mdtf_dgrad(dy, w, x.shape, stride, pads, dil, cd[1], cd[2], cd[4], cd[5])
-        if xs is not None and dx is not None:
-            xs.adopt_or_add(dx)                    # library / v1 dgrad: contribute the tensor
-            dx = None
-        if need_dw and cw[0] == "stem":
-            if sink is not None:
-                stem_wgrad(ctx.stem_x4, dy, w.shape, stride, out=sink.grad)
+            dx, dw = miopen_bwd(x, w, dy, stride, pads, dil, lib_dx, lib_dw)      # (None where not asked for)
+            if lib_dw and sink is not None:
+                sink.grad.add_(dw)                 # straight into the fp32 grad slot
                 dw = V.grad_marker(w)
-            else:
-                dw = stem_wgrad(ctx.stem_x4, dy, w.shape, stride)
-                if dw.dtype != ctx.w_dtype:
-                    dw = dw.to(ctx.w_dtype)
-            ctx.stem_x4 = None
-        elif need_dw and not lib_dw:
-            if sink is not None:
+        xs = ctx.x_sink if need_dx else None
+        if xs is not None and not lib_dx:
+            if (xs.idle() and not xs.completing() and proj_deferrable(w.shape, stride, pads, dil)
+                    and cd.backend in ("mdtf", "pp") and cd.sink_aware):
+                # strided 1x1 projection, first contributor: leave its data gradient to the block's 1x1 conv
+                xs.defer_conv(dy, w, tuple(stride), lambda out, acc, xshape=tuple(x.shape): _launch_dgrad(
+                    cd, dy, w, xshape, stride, pads, dil, out=out, accumulate=acc))
+                need_dx = False
+            elif dual_ok(x.shape, w.shape, stride, pads, dil, xs.pconv) and xs.buf is None and xs.pend is None:
+                fin_job = _dgrad_into_sink(xs, cd, dy, w, x, stride, pads, dil, pconv=xs.take_conv())
+                DUAL_FUSED[0] += 1
+                need_dx = False
+            elif cd.sink_aware:
+                fin_job = _dgrad_into_sink(xs, cd, dy, w, x, stride, pads, dil)
+                need_dx = False
+        if need_dx and not lib_dx:
+            dx = _launch_dgrad(cd, dy, w, x.shape, stride, pads, dil)
+        if xs is not None and dx is not None:
+            xs.adopt_or_add(dx)                    # library / winograd / v1 dgrad: contribute the tensor
+            dx = None
+        if need_dw and not lib_dw:
+            if cw.backend == "stem":
+                dw = stem_wgrad(ctx.stem_x4, dy, w.shape, stride, out=sink.grad if sink is not None else None)
+                ctx.stem_x4 = None
+            elif sink is not None:
                 # fp32 atomics of the wgrad kernel accumulate into the flat gradient buffer
                 if WGRAD_STREAM and x.is_cuda:
                     V.note_accumulate(sink)           # (zeroes a store-first slot the fill skipped)
                     side = _side_stream(x.device)
                     side.wait_stream(torch.cuda.current_stream(x.device))
                     with torch.cuda.stream(side):
-                        mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw[1], cw[2], cw[3], out=sink.grad,
-                                   ver=cw[4], stages=cw[5])
+                        mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw.bm, cw.bn, cw.splits, out=sink.grad,
+                                   ver=cw.ver, stages=cw.stages)
                     x.record_stream(side)
                     dy.record_stream(side)
                     _PENDING.add(x.device)
                 else:
                     # v2 kernels with a split-K slab overwrite the slot as the step's first writer of it
                     # (V.claim_store): no zero fill, no read of the slot in the slab reduction
-                    if cw[4] not in (2, 3):
+                    if not cw.v2:
                         V.note_accumulate(sink)
-                    mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw[1], cw[2], cw[3], out=sink.grad, ver=cw[4],
-                               stages=cw[5], store=sink if cw[4] in (2, 3) else False,
-                               fin=fin_job if cw[4] in (2, 3) else None)
+                    _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil, out=sink.grad,
+                                  store=sink if cw.v2 else False, fin=fin_job if cw.v2 else None)
                     fin_job = None
-                dw = V.grad_marker(w)
             else:
-                dw = mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw[1], cw[2], cw[3], ver=cw[4], stages=cw[5])
-                if dw.dtype != ctx.w_dtype:
-                    dw = dw.to(ctx.w_dtype)
+                dw = _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil)
+            dw = V.grad_marker(w) if sink is not None else dw.to(ctx.w_dtype)
         return dx, dw, None, None, None, None, None
 
 
@@ -1085,12 +1084,16 @@ def _out_hw(x, w, stride, pads, dil):
     return oh, ow
 
 
-def conv2d_nhwc(x, w, stride, pads, dil, bias=None, act=None):
+def _apply(x, w, stride, pads, dil, want_stats):
     if x.dtype != torch.bfloat16:
         raise TypeError("mdtf conv kernels take bf16 activations, got %s" % x.dtype)
     if w.dtype != x.dtype:
         w = w.to(x.dtype)
-    y = _Conv.apply(x, w, tuple(stride), tuple(pads), tuple(dil), _out_hw(x, w, stride, pads, dil), False)
+    return _Conv.apply(x, w, tuple(stride), tuple(pads), tuple(dil), _out_hw(x, w, stride, pads, dil), want_stats)
+
+
+def conv2d_nhwc(x, w, stride, pads, dil, bias=None, act=None):
+    y = _apply(x, w, stride, pads, dil, False)
     if bias is not None or act is not None:
         from . import kernels
         y = kernels.bias_act(y, bias, act)
@@ -1100,12 +1103,7 @@ def conv2d_nhwc(x, w, stride, pads, dil, bias=None, act=None):
 def conv2d_stats_nhwc(x, w, stride, pads, dil, private=False):
     """conv2d that also returns fused BN statistics partials ``(psum, psq, P)`` (or None); ``private``: in a
     buffer of their own (consumed after later convs have run) instead of the shared per-device one."""
-    if x.dtype != torch.bfloat16:
-        raise TypeError("mdtf conv kernels take bf16 activations, got %s" % x.dtype)
-    if w.dtype != x.dtype:
-        w = w.to(x.dtype)
-    y, psum, psq = _Conv.apply(x, w, tuple(stride), tuple(pads), tuple(dil), _out_hw(x, w, stride, pads, dil),
-                               2 if private else True)
+    y, psum, psq = _apply(x, w, stride, pads, dil, 2 if private else True)
     if psum.numel() == 0:
         return y, None
     return y, (psum, psq, psum.shape[0])
@@ -1117,8 +1115,8 @@ def conv2d_dgrad_nhwc(x, w, out_shape, stride, pads):
     kh, kw, wco, wci = w.shape
     wb = w.to(x.dtype).contiguous()
     ch = choose("dgrad", (n, oh, ow, co), (kh, kw, co, wci), stride, pads, (1, 1))
-    if ch[0] == "mdtf":
-        return _ConvT.apply(x, wb, tuple(stride), tuple(pads), (n, oh, ow, co), ch[1], ch[2], ch[4], ch[5])
+    if ch.backend == "mdtf":
+        return _ConvT.apply(x, wb, tuple(stride), tuple(pads), (n, oh, ow, co), ch.bm, ch.bn, ch.ver, ch.stages)
     xc = x.permute(0, 3, 1, 2)
     wt = w.permute(3, 2, 0, 1).to(x.dtype)
     y = F.conv_transpose2d(xc, wt, None, stride, 0)
@@ -1149,6 +1147,6 @@ class _ConvT(torch.autograd.Function):
         dx = mdtf_fwd(dy, w, (oh, ow), stride, pads, (1, 1), bm, bn) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
-            dw = mdtf_wgrad(dy, x, w.shape, stride, pads, (1, 1), 128 if w.shape[0] * w.shape[1] * w.shape[2] >= 128
-                            else 64, 128 if w.shape[3] % 128 == 0 else 64, 0)
+            bm, bn = _default_wgrad_tile(w.shape[0] * w.shape[1] * w.shape[2], w.shape[3])
+            dw = mdtf_wgrad(dy, x, w.shape, stride, pads, (1, 1), bm, bn, 0)
         return dx, dw, None, None, None, None, None, None, None
