@@ -84,6 +84,50 @@ def _conv_nonacti_body(x, in_channels, out_channels, kernel_size, stride):
     return ops.conv2d(x, w, _strides(stride), "SAME", bias=b)
 
 
+def depthwise_conv(layer_name, x, in_channels, kernel_size=(3, 3), stride=(1, 1, 1, 1), channel_multiplier=1):
+    """Depthwise conv (SAME) + bias + ReLU; variables ``depthwise_weights`` and ``biases`` (slim's names)."""
+    with V.variable_scope(layer_name):
+        return _depthwise_body(x, in_channels, kernel_size, stride, channel_multiplier)
+
+
+def depthwise_conv_eval(layer_name, x, in_channels, kernel_size=(3, 3), stride=(1, 1, 1, 1), channel_multiplier=1):
+    """``depthwise_conv`` with AUTO_REUSE."""
+    with V.variable_scope(layer_name, reuse=V.AUTO_REUSE):
+        return _depthwise_body(x, in_channels, kernel_size, stride, channel_multiplier)
+
+
+def _depthwise_weights(in_channels, kernel_size, channel_multiplier):
+    return _variable_with_weight_decay('depthwise_weights',
+                                       [kernel_size[0], kernel_size[1], in_channels, channel_multiplier],
+                                       stddev=5e-2, wd=0.0)
+
+
+def _depthwise_body(x, in_channels, kernel_size, stride, channel_multiplier):
+    w = _depthwise_weights(in_channels, kernel_size, channel_multiplier)
+    b = _variable_on_cpu('biases', [in_channels * channel_multiplier], V.constant_initializer(0.0))
+    return ops.bias_add_relu(ops.depthwise_conv2d(x, w, _strides(stride), "SAME"), b)
+
+
+def depthwise_conv_nonacti(layer_name, x, in_channels, kernel_size=(3, 3), stride=(1, 1, 1, 1),
+                           channel_multiplier=1):
+    """Depthwise conv (SAME), no bias, no activation: the form that precedes :func:`batch_norm`."""
+    with V.variable_scope(layer_name):
+        w = _depthwise_weights(in_channels, kernel_size, channel_multiplier)
+        return ops.depthwise_conv2d(x, w, _strides(stride), "SAME")
+
+
+def separable_conv(layer_name, x, in_channels, out_channels, kernel_size=(3, 3), stride=(1, 1, 1, 1),
+                   channel_multiplier=1):
+    """Depthwise conv (SAME) then a 1x1 conv + bias + ReLU (the ReLU after the pointwise conv only); variables
+    ``depthwise_weights``, ``pointwise_weights`` and ``biases``."""
+    with V.variable_scope(layer_name):
+        dwf = _depthwise_weights(in_channels, kernel_size, channel_multiplier)
+        pwf = _variable_with_weight_decay('pointwise_weights', [1, 1, in_channels * channel_multiplier, out_channels],
+                                          stddev=5e-2, wd=0.0)
+        b = _variable_on_cpu('biases', [out_channels], V.constant_initializer(0.0))
+        return ops.bias_add_relu(ops.separable_conv2d(x, dwf, pwf, _strides(stride), "SAME"), b)
+
+
 def acti_layer(x):
     """ReLU (``:123-128``)."""
     return ops.relu(x)

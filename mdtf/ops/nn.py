@@ -116,6 +116,50 @@ def conv2d_transpose(x, w, output_shape, strides=1, padding="SAME", name=None):
     return y.permute(0, 2, 3, 1)
 
 
+def depthwise_conv2d(input, filter, strides, padding, rate=None, name=None, data_format=None, dilations=None):
+    """``tf.nn.depthwise_conv2d``: NHWC ``input`` [N, H, W, C], ``filter`` [kh, kw, C, channel_multiplier]; output
+    channel ``c * channel_multiplier + m`` is input channel ``c`` convolved with ``filter[:, :, c, m]``.
+
+    ``strides``, ``rate`` and ``dilations`` accept an int, a pair or TF's 4-list; ``padding`` is whatever
+    :func:`conv2d` takes.  bf16 GPU tensors with ``C % 8 == 0``, channel multiplier 1 and at most 49 taps run the
+    direct HIP kernels (``ops/depthwise.py``); CPU tensors, ``MDTF_KERNELS=torch``, fp32 activations, other channel
+    counts and channel multipliers above 1 run the PyTorch expression (a grouped convolution).
+    """
+    if data_format not in (None, "NHWC"):
+        raise ValueError("depthwise_conv2d: data_format must be NHWC, got %r" % (data_format,))
+    if rate is not None and dilations is not None:
+        raise ValueError("depthwise_conv2d: give rate or dilations, not both")
+    n, h, wd, c = input.shape
+    kh, kw, ci, mult = filter.shape
+    if ci != c:
+        raise ValueError("depthwise_conv2d: input has %d channels, filter expects %d" % (c, ci))
+    sh, sw = pair(strides)
+    dh, dw = pair(rate if rate is not None else (dilations if dilations is not None else 1))
+    if (dh > 1 or dw > 1) and (sh > 1 or sw > 1):
+        raise ValueError("depthwise_conv2d: a rate above 1 needs stride 1, got rate %s stride %s" % (
+            (dh, dw), (sh, sw)))
+    oh, ow, pt, pb, pl, pr = conv_geometry(h, wd, kh, kw, (sh, sw), padding, (dh, dw))
+    from . import depthwise
+    if depthwise.native_ok(input, filter):
+        return depthwise.depthwise_nhwc(input, filter, (sh, sw), (pt, pb, pl, pr), (dh, dw), (oh, ow))
+    return _torch_conv_nhwc(input, filter.reshape(kh, kw, 1, c * mult), sh, sw, (pt, pb, pl, pr), dh, dw, groups=c)
+
+
+def separable_conv2d(input, depthwise_filter, pointwise_filter, strides, padding, rate=None, name=None,
+                     data_format=None):
+    """``tf.nn.separable_conv2d``: :func:`depthwise_conv2d`, then :func:`conv2d` with the
+    ``[1, 1, C * channel_multiplier, out]`` pointwise filter at stride 1 (the 1x1 runs on the dense conv kernels)."""
+    c, mult = depthwise_filter.shape[2], depthwise_filter.shape[3]
+    if tuple(pointwise_filter.shape[:2]) != (1, 1):
+        raise ValueError("separable_conv2d: the pointwise filter must be 1x1, got %s" % (
+            tuple(pointwise_filter.shape),))
+    if pointwise_filter.shape[2] != c * mult:
+        raise ValueError("separable_conv2d: the pointwise filter expects %d channels, the depthwise stage gives %d" % (
+            pointwise_filter.shape[2], c * mult))
+    y = depthwise_conv2d(input, depthwise_filter, strides, padding, rate=rate, data_format=data_format)
+    return conv2d(y, pointwise_filter, 1, "VALID")
+
+
 # ---------------------------------------------------------------------------
 # pooling
 # ---------------------------------------------------------------------------
