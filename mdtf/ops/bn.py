@@ -239,8 +239,7 @@ class _BNTrain(torch.autograd.Function):
                     dres = torch.empty_like(x)
         sg, sb = ctx.sinks
         # dgamma/dbeta accumulate straight into the fp32 grad slots when available
-        dgamma = sg.grad if sg is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
-        dbeta = sb.grad if sb is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
+        dgamma, dbeta = V.slot_or_zeros(sg, C, x.device), V.slot_or_zeros(sb, C, x.device)
         if pstats is not None and early is not None:
             from . import conv as _conv
             ws, ev = early
@@ -349,8 +348,7 @@ class _BNTrainDual(torch.autograd.Function):
         M = x.numel() // C
         dx = torch.empty_like(x)
         if DUAL_FUSED and not DUAL_DZ:
-            grads = [sk.grad if sk is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
-                     for sk in ctx.sinks]
+            grads = [V.slot_or_zeros(sk, C, x.device) for sk in ctx.sinks]
             dr = torch.empty_like(r)
             ws = torch.empty(2 * int(N.fn("mdtf_bn_workspace_floats")(M, C)), dtype=torch.float32, device=x.device)
             ps, pq, P = (pstats[0], pstats[1], int(pstats.shape[1])) if pstats is not None else (None, None, 0)
@@ -369,8 +367,7 @@ class _BNTrainDual(torch.autograd.Function):
         # the shortcut BN's output gradient is dy * mask: its backward reads dy and the ReLU mask itself
         # (no masked copy dz is written and re-read); MDTF_DUAL_DZ=1: the written-copy path (A/B, tests)
         dz = torch.empty_like(x) if DUAL_DZ else None
-        grads = [sk.grad if sk is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
-                 for sk in ctx.sinks]
+        grads = [V.slot_or_zeros(sk, C, x.device) for sk in ctx.sinks]
         if pstats is not None:
             from . import conv as _conv
             ws = torch.empty(3 * C, dtype=torch.float32, device=x.device)
@@ -448,8 +445,7 @@ class _BNReluMaxPool(torch.autograd.Function):
         oh, ow, kh, kw, sh, sw, pt, pl = ctx.geo
         dx = torch.empty_like(x)
         sg, sb = ctx.sinks
-        dgamma = sg.grad if sg is not None else torch.zeros(c, dtype=torch.float32, device=x.device)
-        dbeta = sb.grad if sb is not None else torch.zeros(c, dtype=torch.float32, device=x.device)
+        dgamma, dbeta = V.slot_or_zeros(sg, c, x.device), V.slot_or_zeros(sb, c, x.device)
         ws = torch.empty(int(N.fn("mdtf_bn_workspace_floats")(n * h * w, c)), dtype=torch.float32, device=x.device)
         N.check(N.fn("mdtf_maxpool_bn_bwd")(N.ptr(dy), N.ptr(arg), N.ptr(x), N.ptr(dx), n, h, w, c, oh, ow, kh, kw,
                                             sh, sw, pt, pl, N.ptr(g), N.ptr(mean), N.ptr(invstd), N.ptr(dgamma),

@@ -725,12 +725,11 @@ def pp_dgrad(dy, w, x_shape, pads, dil, tile, out=None, accumulate=False, bn_sta
 
 def mdtf_wgrad(x, dy, w_shape, stride, pads, dil, bm, bn, splits, out=None, ver=1, stages=2, store=False, fin=None):
     """fp32 HWIO weight gradient; accumulates into ``out`` when given (must be zeroed or a grad slot).  ``store``:
-    the Variable whose grad slot ``out`` is -- when the launch reduces split-K slabs (v2 kernels), it claims the slot
-    as the step's first writer and overwrites it (V.claim_store); the atomics epilogues accumulate (a claimed slot
-    would need a zeroing launch of its own, which costs more than the fill that covers it).  ``fin``: (activation
+    the Variable whose grad slot is the output (v2 kernels) -- when the launch reduces split-K slabs, it claims the
+    slot as the step's first writer and overwrites it (V.store_slot); the atomics epilogues accumulate (a claimed
+    slot would need a zeroing launch of its own, which costs more than the fill that covers it).  ``fin``: (activation
     sink, statistics buffer, gamma, mean, invstd, M, C) of the BatchNorm whose backward finalize this launch runs
     in extra workgroups (v2 kernels; its result goes to the sink's ``early`` for ops.bn)."""
-    dw = torch.zeros(w_shape, dtype=torch.float32, device=x.device) if out is None else out
     n, h, wd, c = x.shape
     kh, kw, ci, co = w_shape
     if ver in (2, 3):
@@ -742,10 +741,9 @@ def mdtf_wgrad(x, dy, w_shape, stride, pads, dil, bm, bn, splits, out=None, ver=
         slab, cap = wgrad_slab(n * dy.shape[1] * dy.shape[2], kh * kw * ci, co, bm, bn, ver, int(splits), x.device,
                                force=force)
         if store is not False and store is not True:          # a Variable: claim only for the slab reduction
-            var = store
-            store = slab is not None and not WGRAD_INK and V.claim_store(var)
-            if not store:
-                V.note_accumulate(var)
+            claim = slab is not None and not WGRAD_INK
+            out, store = V.store_slot(store) if claim else (V.accumulate_slot(store), False)
+        dw = torch.zeros(w_shape, dtype=torch.float32, device=x.device) if out is None else out
         if store:
             N.fn("mdtf_set_wgrad_store")(1)
         if fin is not None:
@@ -767,6 +765,7 @@ def mdtf_wgrad(x, dy, w_shape, stride, pads, dil, bm, bn, splits, out=None, ver=
         if fin is not None:
             xs.early = (fws, None)
         return dw
+    dw = torch.zeros(w_shape, dtype=torch.float32, device=x.device) if out is None else out
     N.check(N.fn("mdtf_conv_wgrad")(N.ptr(x), N.ptr(dy), N.ptr(dw), n, h, wd, c, dy.shape[1], dy.shape[2], co, kh,
                                     kw, stride[0], stride[1], pads[0], pads[2], dil[0], dil[1], bm, bn, int(splits),
                                     N.stream_ptr()), "conv_wgrad")
@@ -1024,7 +1023,7 @@ class _Conv(torch.autograd.Function):
         if lib_dx or lib_dw:
             dx, dw = miopen_bwd(x, w, dy, stride, pads, dil, lib_dx, lib_dw)      # (None where not asked for)
             if lib_dw and sink is not None:
-                sink.grad.add_(dw)                 # straight into the fp32 grad slot
+                V.accumulate_slot(sink).add_(dw)   # straight into the fp32 grad slot
                 dw = V.grad_marker(w)
         xs = ctx.x_sink if need_dx else None
         if xs is not None and not lib_dx:
@@ -1048,27 +1047,27 @@ class _Conv(torch.autograd.Function):
             dx = None
         if need_dw and not lib_dw:
             if cw.backend == "stem":
-                dw = stem_wgrad(ctx.stem_x4, dy, w.shape, stride, out=sink.grad if sink is not None else None)
+                dw = stem_wgrad(ctx.stem_x4, dy, w.shape, stride, out=V.accumulate_slot(sink))
                 ctx.stem_x4 = None
             elif sink is not None:
                 # fp32 atomics of the wgrad kernel accumulate into the flat gradient buffer
                 if WGRAD_STREAM and x.is_cuda:
-                    V.note_accumulate(sink)           # (zeroes a store-first slot the fill skipped)
+                    slot = V.accumulate_slot(sink)    # (zeroes a store-first slot the fill skipped)
                     side = _side_stream(x.device)
                     side.wait_stream(torch.cuda.current_stream(x.device))
                     with torch.cuda.stream(side):
-                        mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw.bm, cw.bn, cw.splits, out=sink.grad,
+                        mdtf_wgrad(x, dy, w.shape, stride, pads, dil, cw.bm, cw.bn, cw.splits, out=slot,
                                    ver=cw.ver, stages=cw.stages)
                     x.record_stream(side)
                     dy.record_stream(side)
                     _PENDING.add(x.device)
                 else:
                     # v2 kernels with a split-K slab overwrite the slot as the step's first writer of it
-                    # (V.claim_store): no zero fill, no read of the slot in the slab reduction
-                    if not cw.v2:
-                        V.note_accumulate(sink)
-                    _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil, out=sink.grad,
-                                  store=sink if cw.v2 else False, fin=fin_job if cw.v2 else None)
+                    # (V.store_slot in mdtf_wgrad): no zero fill, no read of the slot in the slab reduction
+                    if cw.v2:
+                        _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil, store=sink, fin=fin_job)
+                    else:
+                        _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil, out=V.accumulate_slot(sink))
                     fin_job = None
             else:
                 dw = _launch_wgrad(cw, x, dy, w.shape, stride, pads, dil)

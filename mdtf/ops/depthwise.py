@@ -92,8 +92,7 @@ class _Depthwise(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             sink = ctx.sink
             if sink is not None:                            # straight into the fp32 grad slot
-                V.note_accumulate(sink)
-                wgrad_into(x, dy, geo, sink.grad, True)
+                wgrad_into(x, dy, geo, V.accumulate_slot(sink), True)
                 dw = V.grad_marker(w)
             else:
                 dw = wgrad_into(x, dy, geo, torch.empty(w.shape, dtype=torch.float32, device=w.device), False)

@@ -94,9 +94,9 @@ def _wg_backward(ctx, x, dpre):
     if not (x.dim() == 2 and x.dtype == torch.bfloat16 and dpre.dtype == torch.bfloat16 and _wg_ok(x, dpre)):
         return False
     fuse_b = ctx.has_b and not N.deterministic()
-    # a slot this launch is the step's only writer of is overwritten (V.claim_store: no zero fill, no C read)
-    store = [V.claim_store(sk) for sk in ctx.wsinks]
-    if not mm.wg_into([sk.grad for sk in ctx.wsinks], x, dpre, dbs=[sk.grad for sk in ctx.bsinks] if fuse_b else None,
+    # a slot this launch is the step's first writer of is overwritten (V.store_slot: no zero fill, no C read)
+    gws, store = zip(*[V.store_slot(sk) for sk in ctx.wsinks])
+    if not mm.wg_into(gws, x, dpre, dbs=[V.accumulate_slot(sk) for sk in ctx.bsinks] if fuse_b else None,
                       store=store):
         for sk, st in zip(ctx.wsinks, store):
             if st:                         # not launched: the fallback accumulates into a zeroed slot
@@ -105,7 +105,7 @@ def _wg_backward(ctx, x, dpre):
     if ctx.has_b and not fuse_b:
         col = 0
         for j, n in enumerate(ctx.widths):
-            kernels.colsum_into(dpre[:, col:col + n].contiguous(), ctx.bsinks[j].grad)
+            kernels.colsum_into(dpre[:, col:col + n].contiguous(), V.accumulate_slot(ctx.bsinks[j]))
             col += n
     return True
 
@@ -581,10 +581,10 @@ class _Dense(torch.autograd.Function):
             sink = ctx.wsinks[j]
             if sink is not None:
                 if ctx.trans:
-                    _accum_mm(sink.grad, d.t(), x)
+                    _accum_mm(V.accumulate_slot(sink), d.t(), x)
                 else:
                     bsink = ctx.bsinks[j] if ctx.has_b else None
-                    if wgrad_into(sink.grad, x, d, bsink.grad if bsink is not None else None):
+                    if wgrad_into(V.accumulate_slot(sink), x, d, V.accumulate_slot(bsink)):
                         bias_done[j] = True
                 gws.append(V.grad_marker(ws[j]))
             elif ctx.needs_input_grad[8 + j]:
@@ -594,25 +594,12 @@ class _Dense(torch.autograd.Function):
                 gws.append(None)
         if ctx.has_b and all(bias_done):
             gbs = [V.grad_marker(b) for b in bs]    # summed inside the weight-gradient kernel
-        elif ctx.has_b and any(bias_done):
-            tot = kernels.colsum(dpre)
-            col = 0
-            for j, n in enumerate(ctx.widths):
-                part = tot[col:col + n]
-                col += n
-                if bias_done[j]:
-                    gbs.append(V.grad_marker(bs[j]))
-                elif ctx.bsinks[j] is not None:
-                    ctx.bsinks[j].grad.add_(part)
-                    gbs.append(V.grad_marker(bs[j]))
-                else:
-                    gbs.append(part.to(bs[j].dtype))
         elif ctx.has_b:
             fused = None
-            if ctx.nw > 1 and all(sk is not None for sk in ctx.bsinks):
-                fused = _adjacent([sk.grad for sk in ctx.bsinks])     # q|k|v slots back to back
+            if ctx.nw > 1 and not any(bias_done) and all(sk is not None for sk in ctx.bsinks):
+                fused = _adjacent([V.accumulate_slot(sk) for sk in ctx.bsinks])     # q|k|v slots back to back
             if ctx.nw == 1 and ctx.bsinks[0] is not None:
-                kernels.colsum_into(dpre, ctx.bsinks[0].grad)
+                kernels.colsum_into(dpre, V.accumulate_slot(ctx.bsinks[0]))
                 gbs.append(V.grad_marker(bs[0]))
             elif fused is not None:
                 kernels.colsum_into(dpre, fused)
@@ -624,7 +611,8 @@ class _Dense(torch.autograd.Function):
                     part = tot[col:col + n]
                     col += n
                     if ctx.bsinks[j] is not None:
-                        ctx.bsinks[j].grad.add_(part)
+                        if not bias_done[j]:           # (else: summed inside the weight-gradient kernel)
+                            V.accumulate_slot(ctx.bsinks[j]).add_(part)
                         gbs.append(V.grad_marker(bs[j]))
                     else:
                         gbs.append(part.to(bs[j].dtype))
@@ -644,12 +632,12 @@ def _pp_weight_grads(ctx, x, dpre, ws, bs):
         done = True
     elif all_w and (all_b or not ctx.has_b) and PP_WGRAD == "all":
         if ctx.trans:                                   # w [N, K]: g += dy^T x  (C rows = N)
-            done = ctx.nw == 1 and mm.wgrad_into([wsinks[0].grad], dpre, x, dbs=None)
+            done = ctx.nw == 1 and mm.wgrad_into([V.accumulate_slot(wsinks[0])], dpre, x, dbs=None)
             if done and ctx.has_b:
-                kernels.colsum_into(dpre, bsinks[0].grad)
+                kernels.colsum_into(dpre, V.accumulate_slot(bsinks[0]))
         else:
-            done = mm.wgrad_into([sk.grad for sk in wsinks], x, dpre,
-                                 dbs=[sk.grad for sk in bsinks] if ctx.has_b else None)
+            done = mm.wgrad_into([V.accumulate_slot(sk) for sk in wsinks], x, dpre,
+                                 dbs=[V.accumulate_slot(sk) for sk in bsinks] if ctx.has_b else None)
     if done:
         gws = [V.grad_marker(w) for w in ws]
         if ctx.has_b:
@@ -663,10 +651,10 @@ def _pp_weight_grads(ctx, x, dpre, ws, bs):
             bias_done = False
             if sink is not None:
                 if ctx.trans:
-                    _accum_mm(sink.grad, d.t(), x)
+                    _accum_mm(V.accumulate_slot(sink), d.t(), x)
                 else:                                   # conv-kernel wgrad, bias gradient fused in
                     bsk = bsinks[j] if ctx.has_b else None
-                    bias_done = wgrad_into(sink.grad, x, d, bsk.grad if bsk is not None else None)
+                    bias_done = wgrad_into(V.accumulate_slot(sink), x, d, V.accumulate_slot(bsk))
                 gws[j] = V.grad_marker(ws[j])
             elif ctx.needs_input_grad[8 + j]:
                 g = torch.mm(d.t(), x) if ctx.trans else torch.mm(x.t(), d)
@@ -674,7 +662,8 @@ def _pp_weight_grads(ctx, x, dpre, ws, bs):
             if ctx.has_b and bias_done:
                 gbs[j] = V.grad_marker(bs[j])
             elif ctx.has_b and bsinks[j] is not None:
-                kernels.colsum_into(d, bsinks[j].grad) if d.is_contiguous() else bsinks[j].grad.add_(d.float().sum(0))
+                slot = V.accumulate_slot(bsinks[j])
+                kernels.colsum_into(d, slot) if d.is_contiguous() else slot.add_(d.float().sum(0))
                 gbs[j] = V.grad_marker(bs[j])
             elif ctx.has_b:
                 gbs[j] = d.float().sum(0).to(bs[j].dtype)
@@ -826,9 +815,10 @@ class _TiedDecoder(torch.autograd.Function):
         except (RuntimeError, TypeError):
             dh = torch.mm(dp, Wp)
         # the decoder's weight gradient writes the whole (padded) slot: as the step's first writer it overwrites it
-        # (V.claim_store; the word embedding's scatter-add accumulates onto it later)
-        _accum_mm(wv.grad_padded, dp.t(), h, store=V.claim_store(wv))
-        kernels.colsum_into(dp, bv.grad_padded)
+        # (V.store_slot; the word embedding's scatter-add accumulates onto it later)
+        gw, store = V.store_slot(wv, padded=True)
+        _accum_mm(gw, dp.t(), h, store=store)
+        kernels.colsum_into(dp, V.accumulate_slot(bv, padded=True))
         w, b = ctx.like
         return dh, V.grad_marker(w), V.grad_marker(b)
 
@@ -837,6 +827,7 @@ def tied_decoder(x, w, b):
     """``x @ w^T + b`` for a tied decoder: the padded path when both variables carry padded flat views (set
     ``pad_rows`` from :func:`decoder_pad_rows` before the flat space is built), else :func:`dense_transposed`."""
     wv, bv = getattr(w, "_mdtf_var", None), getattr(b, "_mdtf_var", None)
+    # (eligibility only: do the padded views exist and match; the backward gets them from V.store_slot)
     ok = (DEC_SPLIT > 0 and wv is not None and bv is not None and x.dim() == 2 and x.is_cuda
           and x.dtype == torch.bfloat16 and wv.shadow_padded is not None and wv.grad_padded is not None
           and bv.grad_padded is not None and (bv.shadow_padded is not None or bv.master_padded is not None)

@@ -76,7 +76,7 @@ class _BiasAct(torch.autograd.Function):
         if ctx.has_bias:
             C = dx.shape[-1]
             if ctx.sink is not None:       # column sums accumulate straight into the fp32 grad slot
-                colsum_into(dx.view(-1, C), ctx.sink.grad)
+                colsum_into(dx.view(-1, C), V.accumulate_slot(ctx.sink))
                 db = V.grad_marker(ctx.bias)
             else:
                 db = colsum(dx.reshape(-1, C)).to(ctx.bias_dtype)

@@ -48,13 +48,6 @@ def _seed_off(p_drop, device):
     return rng_offset_tensor(device)
 
 
-def _sink_or_zeros(t, n, device):
-    var = V.grad_sink(t) if t is not None else None
-    if var is not None:
-        return var, var.grad
-    return None, torch.zeros(n, dtype=torch.float32, device=device)
-
-
 class _LayerNorm(torch.autograd.Function):
     """y = LN(dropout_p(x) + residual) with the dropout mask regenerated from a counter hash."""
 
@@ -103,8 +96,7 @@ class _LayerNorm(torch.autograd.Function):
         ds = torch.empty_like(s)
         dxb = torch.empty_like(s) if p_drop > 0 else None     # gradient of the dropped-out branch input
         sg, sb = ctx.sinks
-        dg = sg.grad if sg is not None else torch.zeros(H, dtype=torch.float32, device=s.device)
-        db = sb.grad if sb is not None else torch.zeros(H, dtype=torch.float32, device=s.device)
+        dg, db = V.slot_or_zeros(sg, H, s.device), V.slot_or_zeros(sb, H, s.device)
         ws = torch.empty(N.fn("mdtf_ln_bwd_ws")(rows, H), dtype=torch.float32, device=s.device)
         from . import conv as _conv
         # gamma / beta in grad slots (read after the join at the end of backward): the partial reduction may leave
@@ -200,7 +192,7 @@ class _Embed(torch.autograd.Function):
         vocab, H = ctx.shape
         dy = dy.contiguous()
         sink = ctx.sink
-        dt = sink.grad if sink is not None else torch.zeros((vocab, H), dtype=torch.float32, device=dy.device)
+        dt = V.slot_or_zeros(sink, (vocab, H), dy.device)
         if N.deterministic():
             # sorted (deterministic) scatter-add instead of the atomic kernel
             prev = torch.are_deterministic_algorithms_enabled()
@@ -259,8 +251,7 @@ class _BertEmbed(torch.autograd.Function):
         word, pos, typ = ctx.like
         H = word.shape[1]
         dy = dy.contiguous()
-        bufs = [sk.grad if sk is not None else torch.zeros(t.shape, dtype=torch.float32, device=dy.device)
-                for sk, t in zip(ctx.sinks, ctx.like)]
+        bufs = [V.slot_or_zeros(sk, t.shape, dy.device) for sk, t in zip(ctx.sinks, ctx.like)]
         N.check(N.fn("mdtf_bert_embed_bwd")(N.ptr(dy), N.ptr(ids), N.ptr(types), N.ptr(bufs[0]), N.ptr(bufs[1]),
                                             N.ptr(bufs[2]), B, S_, H, word.shape[0], typ.shape[0], N.stream_ptr()),
                 "bert_embed_bwd")
@@ -287,7 +278,7 @@ class _AddPositions(torch.autograd.Function):
         B, S_, H = dy.shape
         dy = dy.contiguous()
         sink = ctx.sink
-        dt = sink.grad if sink is not None else torch.zeros(ctx.like.shape, dtype=torch.float32, device=dy.device)
+        dt = V.slot_or_zeros(sink, ctx.like.shape, dy.device)
         K.colsum_into(dy.view(B, S_ * H), dt[:S_].view(S_ * H))
         if sink is not None:
             return dy, V.grad_marker(ctx.like)

@@ -225,9 +225,12 @@ class _VarRead(torch.autograd.Function):
         var = ctx.var
         if var.grad is None:
             var.grad = torch.zeros_like(var.master)
-        if not _is_marker(g):             # a sink-only gradient was already accumulated in place
+        if not _is_marker(g):
             note_accumulate(var)
             var.grad.add_(g)              # one kernel, dtype promotion included
+        elif getattr(var, "written_epoch", -1) != GRAD_EPOCH[0]:      # a marker: some kernel wrote the slot in place
+            raise RuntimeError("gradient slot of %s was written in place by a writer that did not go through "
+                               "accumulate_slot / store_slot" % var.name)
         grad_done(var)
         return None, None, None
 
@@ -255,8 +258,8 @@ def grad_sink(t):
 
     Returns the Variable when ``t`` is the value a Variable handed to the model
     (under grad mode) and its grad slot exists, else None.  A backward that
-    uses the sink *adds* its gradient into ``var.grad`` (zeroed at the start of
-    every step) and returns :func:`grad_marker` as the autograd gradient of
+    uses the sink writes its gradient into the slot :func:`accumulate_slot` or
+    :func:`store_slot` hands it and returns :func:`grad_marker` as the autograd gradient of
     ``t``; ``_VarRead.backward`` then skips the add (or adds only the other
     consumers' gradients) and fires the bucket hook as usual.  This removes the
     zero/cast/add kernels between a weight-gradient kernel and the flat
@@ -268,13 +271,14 @@ def grad_sink(t):
     return var
 
 
-# Store-first gradient slots (MDTF_GRAD_STORE_FIRST, on by default): a weight-gradient kernel that writes every
-# element of a slot and is the step's FIRST writer of it overwrites it instead of accumulating (the other writers
-# of the step -- a shared weight's other consumers -- accumulate onto it).  A variable whose first write of a step was such a store is not zeroed at the start of the next
-# step (parallel/flat.py skips its range in the one zero-fill launch), which removes its share of the gradient
-# buffer fill and the read of C in the kernel's epilogue.  Safety nets: any other first write into a skipped slot
-# zeroes it first (note_accumulate, _VarRead.backward), and a skipped slot nobody wrote in a step is zeroed at the
-# end of backward (unclaimed_skips).
+# Store-first gradient slots (MDTF_GRAD_STORE_FIRST, on by default): a kernel that writes every element of a slot
+# and is the step's FIRST writer of it overwrites it instead of accumulating (the step's other writers -- a shared
+# weight's other consumers -- accumulate onto it), and the next step's zero fill leaves that slot out
+# (parallel/flat.py): no fill of it, no read of C in the kernel's epilogue.  Whoever writes it first in that step
+# must then store again or zero it before adding.  The rule: ops code never reads ``.grad`` of a sink; it asks
+# accumulate_slot() (a writer that adds) or store_slot() (a kernel that writes every element) for the tensor, which
+# declares the write and zeroes a skipped slot where needed.  _VarRead.backward refuses a marker whose slot was not
+# declared this step; a skipped slot nobody wrote in a step is zeroed at the end of backward (unclaimed_skips).
 GRAD_EPOCH = [0]
 STORE_FIRST = os.environ.get("MDTF_GRAD_STORE_FIRST", "1") != "0"
 
@@ -312,6 +316,25 @@ def note_accumulate(var):
     var.store_first = False
     if getattr(var, "skip_zero", False) and var.grad is not None:
         var.grad.zero_()
+
+
+def accumulate_slot(var, padded=False):
+    """The gradient slot of ``var`` (``padded``: with its pad rows) for a writer that adds into it; None for None."""
+    if var is not None:
+        note_accumulate(var)
+        return var.grad_padded if padded else var.grad
+
+
+def store_slot(var, padded=False):
+    """``(slot, store)`` for a kernel that writes every element of the slot: it overwrites when ``store``
+    (claim_store), else it accumulates; the write is declared either way."""
+    store = claim_store(var)
+    return (var.grad_padded if padded else var.grad) if store else accumulate_slot(var, padded), store
+
+
+def slot_or_zeros(var, shape, device):
+    """The slot of the sink ``var`` to accumulate into, or a zeroed fp32 buffer where there is no sink."""
+    return accumulate_slot(var) if var is not None else torch.zeros(shape, dtype=torch.float32, device=device)
 
 
 def unclaimed_skips(variables):

@@ -844,6 +844,88 @@ def test_grad_store_first_matches_zero_and_accumulate(monkeypatch):
         assert torch.allclose(runs[True][1][k], g, rtol=1e-4, atol=1e-6), k
 
 
+def _stored_then_fallback(monkeypatch, shapes, step):
+    """Two steps over one flat group, with store-first on and off: ``step(i, variables, generator)`` runs forward and
+    backward of step A (i = 0: a kernel that claims the first ``shapes`` slot(s)) and step B (i = 1: a writer that
+    accumulates).  Step B's slots must equal the store-first-off run's, and a slot that kept step A's sum would be
+    caught by that comparison."""
+    runs = {on: _two_steps(monkeypatch, on, shapes, step) for on in (True, False)}
+    (on_a, on_b), stored = runs[True]
+    ref_a, ref_b = runs[False][0]
+    assert not any(runs[False][1][0])
+    for k in range(len(shapes)):
+        print("slot %d: max |on - off| %.3e, max |off| %.3e" % (k, float((on_b[k] - ref_b[k]).abs().max()),
+                                                               float(ref_b[k].abs().max())))
+        assert torch.allclose(on_b[k], ref_b[k], rtol=1e-4, atol=1e-6), k
+        assert not torch.allclose(ref_b[k], ref_a[k] + ref_b[k], rtol=1e-4, atol=1e-6), k    # a stale sum shows
+    return stored
+
+
+def _two_steps(monkeypatch, on, shapes, step):
+    from mdtf.parallel.flat import FlatGroup
+    from mdtf.train import variables as V
+    monkeypatch.setattr(V, "STORE_FIRST", on)
+    gen = torch.Generator().manual_seed(11)
+    vs = [V.Variable("v%d" % i, torch.randn(s, generator=gen) * 0.05) for i, s in enumerate(shapes)]
+    g = FlatGroup(vs, DEV, torch.bfloat16, False)
+    grads, stored = [], []
+    for i in range(2):
+        V.begin_grad_epoch()
+        g.zero_grad(skip_stored=True)
+        for v in vs:
+            v.uses = 0
+        step(i, vs, gen)
+        V.unclaimed_skips(vs)
+        torch.cuda.synchronize()
+        grads.append([v.grad.detach().cpu().clone() for v in vs])
+        stored.append([bool(getattr(v, "store_first", False)) for v in vs])
+    return grads, stored
+
+
+@pytest.mark.parametrize("nw", [1, 3])
+def test_dense_fallback_after_store_first_step(nw, monkeypatch):
+    """A dense layer (nw = 3: q|k|v through dense_multi) whose weight gradient runs on csrc/gemm_wg.hip over 4096
+    tokens (the slots are claimed and stored) and on the conv-kernel fallback over 2048 tokens the step after
+    (_wg_ok fails): the fallback zeroes the slots the fill skipped before it accumulates."""
+    from mdtf.ops import gemm as G
+    monkeypatch.setenv("MDTF_WG_SQUARE", "1")
+
+    def step(i, vs, gen):
+        tokens = (4096, 2048)[i]
+        x = torch.randn(tokens, 128, generator=gen).to(DEV).bfloat16()
+        reads = [v.read(torch.bfloat16) for v in vs]
+        y = G.dense_multi(x, reads[:nw], reads[nw:])
+        y.backward((torch.randn(y.shape, generator=gen) / 64).to(DEV).bfloat16())
+    stored = _stored_then_fallback(monkeypatch, [(128, 128)] * nw + [(128,)] * nw, step)
+    assert all(stored[0][:nw]), stored               # step A: every weight slot was store-written
+
+
+def test_conv_library_wgrad_after_slab_store_step(monkeypatch):
+    """A conv whose table entry selects the v2 weight-gradient kernel with a split-K slab (2 slabs: the reduction
+    stores into the claimed slot) in one step and the library in the next.  The library returns its weight gradient
+    in bf16 and sums in an order that differs run to run (two store-first-off runs of random operands differed by
+    one bf16 ulp, 1.2e-4, in 1 of 36864 elements), so step B's operands are small integers over 64: every partial
+    sum is exact in bf16 and the comparison sees the slot bookkeeping alone."""
+    from mdtf.ops import conv as C
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+    monkeypatch.delenv("MDTF_CONV", raising=False)
+    for flag, value in dict(_SLAB_MODE="dense", WGRAD_INK=False, WGRAD_STREAM=False).items():
+        monkeypatch.setattr(C, flag, value)
+    key = "wgrad:2,8,8,64:3,3,64:1,1:1,1,1,1:1,1"
+    entries = [{"backend": "mdtf", "bm": 128, "bn": 64, "splits": 0, "ver": 2, "stages": 2, "slab": True},
+               {"backend": "miopen"}]
+
+    def step(i, vs, gen):
+        monkeypatch.setattr(C, "_TABLE", {key: entries[i]})
+        draw = (lambda s: torch.randn(s, generator=gen)) if i == 0 else \
+            (lambda s: torch.randint(-1, 2, s, generator=gen).float())      # |dw| <= 128 / 64: exact in bf16
+        x = draw((2, 8, 8, 64)).to(DEV).bfloat16()
+        y = C.conv2d_nhwc(x, vs[0].read(torch.bfloat16), (1, 1), (1, 1, 1, 1), (1, 1))
+        y.backward((draw(tuple(y.shape)) / 64).to(DEV).bfloat16())
+    stored = _stored_then_fallback(monkeypatch, [(3, 3, 64, 64)], step)
+    assert stored[0][0], stored                      # step A took the slab reduction and claimed the slot
+
+
 def test_fill_ranges_zero():
     """csrc/kernels.hip fill_ranges_kernel: zeroes exactly the given ranges (odd starts / lengths, float4 and
     scalar paths, ranges across 4096-element block boundaries)."""
