@@ -2672,7 +2672,19 @@ ConvArgs make_args(int N, int H, int W, int Cin, int OH, int OW, int Cout, int K
   return a;
 }
 
+// 3x3, stride 1, pad 1, no dilation, C -> C on the same pixel grid: what conv_img.hip serves (it picks the sizes)
+bool conv_img_geometry(int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int SH, int SW, int PH,
+                       int PW, int DH, int DW) {
+  return KH == 3 && KW == 3 && SH == 1 && SW == 1 && PH == 1 && PW == 1 && DH == 1 && DW == 1 && Cin == Cout &&
+         OH == H && OW == W;
+}
+
 }  // namespace
+
+// conv_img.hip
+MDTF_EXPORT int mdtf_conv_img_routed(int H, int W, int C, int wmode);
+MDTF_EXPORT int mdtf_conv3_img(const void* src, const void* wgt, void* out, int N, int H, int W, int C, int wmode,
+                               float* s0, float* s1, int slots, const void* bx, const void* bmask, hipStream_t st);
 
 // Y = conv(X, W); optional per-M-tile BN partials (stat_sum/stat_sq [mtiles][Cout]).
 // Returns the number of M tiles through *mtiles_out (for the BN finalize).
@@ -2735,6 +2747,13 @@ MDTF_EXPORT int mdtf_conv_fwd_v2(const void* x, const void* wt, void* y, float* 
                                  hipStream_t st) {
   if (Cin % 64 || Cout % 8) return MDTF_EINVAL;
   if (KH * KW > 32 || (long long)N * H * W * Cin * 2 > 0x7fffffffLL) return MDTF_EUNSUPPORTED;
+  // the image-resident kernel (conv_img.hip) takes its geometries whatever the tile code says
+  if (conv_img_geometry(H, W, Cin, OH, OW, Cout, KH, KW, SH, SW, PH, PW, DH, DW) && (!stat_sum) == (!stat_sq) &&
+      mdtf_conv_img_routed(H, W, Cin, 0)) {
+    if (mtiles_out) *mtiles_out = N * (H / 14);
+    return mdtf_conv3_img(x, wt, y, N, H, W, Cin, 0, stat_sum, stat_sq, stat_slots > 0 ? stat_slots : kStatSlots,
+                          nullptr, nullptr, st);
+  }
   ConvArgs a = make_args(N, H, W, Cin, OH, OW, Cout, KH, KW, SH, SW, PH, PW, DH, DW);
   a.src = (const bf16_t*)x;
   a.wgt = (const bf16_t*)wt;
@@ -2765,6 +2784,10 @@ MDTF_EXPORT int mdtf_conv_dgrad_v2(const void* dy, const void* w, void* dx, int 
   if ((SH != 1 || SW != 1) && (DH != 1 || DW != 1)) return MDTF_EUNSUPPORTED;
   // <= 32 taps per K walk (per stride-parity class when strided)
   if (ceil_div(KH, SH) * ceil_div(KW, SW) > 32) return MDTF_EUNSUPPORTED;
+  // the image-resident kernel (conv_img.hip): plain or BN-backward-statistics epilogue, nothing accumulated
+  if (conv_img_geometry(H, W, Cin, OH, OW, Cout, KH, KW, SH, SW, PH, PW, DH, DW) && !accumulate && !acc_src &&
+      !acc_mask && (!bsum) == (!bsq) && (!bsum || bx) && mdtf_conv_img_routed(H, W, Cin, 1))
+    return mdtf_conv3_img(dy, w, dx, N, H, W, Cin, 1, bsum, bsq, bslots > 0 ? bslots : 1, bx, bmask, st);
   ConvArgs a = make_args(N, H, W, Cin, OH, OW, Cout, KH, KW, SH, SW, PH, PW, DH, DW);
   a.src = (const bf16_t*)dy;
   a.wgt = (const bf16_t*)w;

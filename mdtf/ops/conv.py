@@ -553,6 +553,26 @@ def ws_depth_ok(k_total, d):
     return ks > 4 and d in (3, 4, 6) and ks % d == 0
 
 
+# image-resident 3x3 kernel (csrc/conv_img.hip): chosen inside mdtf_conv_fwd_v2 / mdtf_conv_dgrad_v2 by the
+# MDTF_CONV_IMG mask (1 / 2: 28x28x128 forward / data gradient, 4 / 8: 14x14x256); these only read or override it
+N.register("mdtf_conv_img_mask", [])
+N.register("mdtf_set_conv_img_mask", [N.I], None)
+N.register("mdtf_conv_img_routed", [N.I] * 4)
+
+
+def conv_img_mask():
+    return N.fn("mdtf_conv_img_mask")()
+
+
+def set_conv_img_mask(mask):
+    """Override the (shape, pass) mask for this process; a negative value restores the environment's."""
+    N.fn("mdtf_set_conv_img_mask")(int(mask))
+
+
+def conv_img_routed(h, w, c, dgrad):
+    return bool(N.fn("mdtf_conv_img_routed")(h, w, c, int(bool(dgrad))))
+
+
 N.register("mdtf_conv3_rows", [N.P, N.P, N.P] + [N.I] * 4 + [N.P, N.P, N.I, N.P, N.P, N.P])
 # row-staged 3x3 kernel (csrc/conv_rows.hip) for the 64 -> 64 channel, 56-wide stride-1 convolutions the
 # weight-stationary table entries name; MDTF_CONV_ROWS=0 keeps the streamed kernel

@@ -14,9 +14,11 @@ import re
 import sys
 
 WS = r"conv_ws_kernel<\d+, \d+, \d+, \d+, \d+, "     # ...<TP, NW, CG, D, KSC, EPI, DIRECT>
-CATS = [("conv_fwd", r"conv_fd_v2<\d+, \d+, 0, |conv_fd_kernel<\d+, \d+, 0,|conv_pp|" + WS + r"1,|stem_pack4|stem_conv_rows"),
-        ("conv_dgrad", r"conv_fd_v2<\d+, \d+, [12], |conv_fd_kernel<\d+, \d+, [12],|dgrad_zero_classes|" + WS + r"[234],"),
-        ("conv_ws_plain", WS + r"0,"), ("conv_wgrad", r"conv_wgrad|stem_wgrad"),
+# conv3_img<EPI, W, C>: the name carries the epilogue, not the pass.  Forward BN statistics (EPI 1) are forwards,
+# BN-backward statistics (3) data gradients; a plain store (0) can be either, so it has a category of its own
+CATS = [("conv_fwd", r"conv_fd_v2<\d+, \d+, 0, |conv_fd_kernel<\d+, \d+, 0,|conv_pp|conv3_img<1, |" + WS + r"1,|stem_pack4|stem_conv_rows"),
+        ("conv_dgrad", r"conv_fd_v2<\d+, \d+, [12], |conv_fd_kernel<\d+, \d+, [12],|dgrad_zero_classes|conv3_img<3, |" + WS + r"[234],"),
+        ("conv_ws_plain", WS + r"0,"), ("conv_img_plain", r"conv3_img<0, "), ("conv_wgrad", r"conv_wgrad|stem_wgrad"),
         ("winograd", r"wino"),
         ("miopen", r"^(naive_conv|igemm|MIOpen|miopen|ck::|gridwise|sp3A|kernel_batched|SubTensor|_ZN2ck)"),
         ("bn_apply", r"bn_apply|bn_relu_maxpool"), ("bn_dx", r"bn_dx|maxpool_bn"), ("bn_reduce", r"bn_reduce"),
