@@ -1,22 +1,24 @@
-"""Dense / matmul on the GPU: hand-written MFMA kernels where they win, hipBLASLt GEMMs elsewhere,
-fp32 weight-gradient sinks.
+"""Dense / matmul on the GPU: every product of a dense layer runs on a named engine, picked by one small
+function per pass from the shapes, the module flags and what the layer feeds (``_fwd_route``, ``_dgrad_route``,
+``_wgrad_first``).  A kernel that does not take a shape hands the product on to the next engine; the library
+(hipBLASLt through ``torch.mm`` / ``torch.addmm``) takes everything.
 
-Forward: ``y = act(x @ W + b)`` in ONE hand-written MFMA launch (``hand_fwd``: the fd v2 kernel's MODE 3
-reads W in place through transposed LDS fragment reads, adds the bias to the fp32 accumulators and applies
-GELU/ReLU in the epilogue, also storing the pre-activation GELU's backward needs).  Several weight matrices
-that share an input (BERT's query/key/value) are column segments of the same launch, with no concatenated
-copy.  Shapes it does not take (and ``MDTF_DENSE_FWD=hipblaslt``) use ``addmm`` (hipBLASLt, bias epilogue)
-plus the mdtf activation kernel.
+* forward ``y = act(x @ [W_0|..] + b)``: ``core`` (csrc/gemm_pp.hip: bias / activation epilogue, q|k|v as column
+  segments of one launch; by default the products with a fused activation and the shapes of
+  ``MDTF_PP_FWD_SHAPES``), ``hand`` (the conv kernel's MODE 3, opt-in by ``FWD_TILES`` / ``MDTF_DENSE_FWD=mdtf``),
+  ``library`` (``addmm`` plus the activation kernel).
+* data gradient ``dx = dpre @ W^T``: ``core`` / ``core+act`` (the producer's activation backward in the epilogue),
+  ``hand+act`` (the conv kernel's MODE 4: ffn()'s second layer by default), ``hand`` (``MDTF_DENSE_DGRAD=mdtf``),
+  ``library``; accumulated inside the GEMM into a fanned-out input's gradient sink.
+* weight (+ bias) gradient, straight into the variables' fp32 gradient slots: ``wg`` (csrc/gemm_wg.hip, q|k|v in
+  one launch, bias column sums fused), ``core``, ``per-segment`` (the conv kernel's weight gradient run as a 1x1
+  convolution, bias sums from an all-ones MFMA; hipBLASLt ``C += A^T B`` and the column-sum kernel below it).
 
-Backward: ``dx = dpre @ W^T`` (bf16; hipBLASLt, or with ``MDTF_DENSE_DGRAD=mdtf`` the mdtf v2 dgrad kernel
-for the shapes of ``DGRAD_TILES``; accumulated inside the GEMM into a fanned-out input's gradient sink), and the weight gradient is the mdtf weight-gradient
-kernel (``csrc/conv_igemm.hip`` conv_wgrad_v2 run as a 1x1 convolution) writing
-*directly into the variable's fp32 gradient slot*.  The same kernel adds the bias
-gradient (the column sums of ``dpre``) from the B fragments it already holds, with an
-all-ones MFMA, so no bf16 weight gradient is materialised and no column-sum kernel runs.
-Shapes the kernel does not take fall back to hipBLASLt ``C += A^T B`` (bf16 inputs, fp32
-output) and the two-stage column-sum kernel.
+A layer that ``MDTF_PP_FWD``'s policy covers belongs to the core's family: its backward reads the weight segments
+in place.  The other layers (all of them under ``MDTF_DENSE=legacy``, for A/B comparisons) save their concatenated
+weight for the backward.
 """
+import contextlib
 import os
 
 import torch
@@ -62,7 +64,6 @@ DENSE_WGRAD_STREAM = os.environ.get("MDTF_DENSE_WGRAD_STREAM", "0") == "1"
 
 def _wgrad_section(ctx, x, dpre):
     """Context for a dense backward's weight-gradient section: the side stream when enabled and safe."""
-    import contextlib
     sinks = list(ctx.wsinks) + (list(ctx.bsinks) if ctx.has_b else [])
     # every output must be a slot, and this must be each slot's last contribution of the step (uses == 1): an
     # earlier main-stream writer is ordered by the wait below, a later one would race the side stream
@@ -83,16 +84,62 @@ def _dgrad_shape_on(ws):
     return bool(PP_DGRAD_SHAPES) and "%dx%d" % (sum(w.shape[1] for w in ws), ws[0].shape[0]) in PP_DGRAD_SHAPES
 
 
+# The engine of each product, by name (as ops.conv.choose() names a conv's).  A route is the engine that gets the
+# product first: a kernel that does not take the shape hands it on (forward and data gradient: to the library;
+# weight gradient: to the per-segment loop).
+FWD_CORE, FWD_HAND, FWD_LIBRARY = "core", "hand", "library"
+DGRAD_CORE, DGRAD_CORE_ACT, DGRAD_HAND_ACT, DGRAD_HAND = "core", "core+act", "hand+act", "hand"
+DGRAD_LIBRARY = "library"
+WGRAD_WG, WGRAD_CORE, WGRAD_SEGMENTS = "wg", "core", "per-segment"
+
+
+def _fwd_route(x, ws, act, nw, trans):
+    """``(route, pp)`` of a layer's forward.  ``pp``: the layer belongs to the core's family -- MDTF_PP_FWD's policy
+    covers it, whichever engine then computes it -- and its backward reads the weight segments in place; the other
+    layers save their concatenated weight and try the hand-written kernels."""
+    core = PP_FWD == "all" or (PP_FWD == "fused" and (act != 0 or nw > 1)) or (PP_FWD == "act" and act != 0)
+    if not core and PP_FWD_SHAPES and not trans:
+        core = "%dx%d" % (x.shape[1], sum(w.shape[1] for w in ws)) in PP_FWD_SHAPES
+    pp = (PP and (core or PP_FWD != "act") and x.is_cuda and x.dtype == torch.bfloat16 and x.stride(1) == 1
+          and N.use_native(x) and all(w.is_contiguous() and w.dtype == torch.bfloat16 for w in ws))
+    if pp and trans:            # x @ w^T, w [N, K], is the core's data-gradient layout: all or nothing
+        pp = core = nw == 1 and act == 0 and PP_FWD == "all"
+    if pp:
+        return (FWD_CORE if core else FWD_LIBRARY), True
+    return (FWD_LIBRARY if trans else FWD_HAND), False
+
+
+def _dgrad_route(pp, ws, nw, trans, act_pre, sink):
+    """The route of ``dx = dpre @ W^T``.  ``act_pre``: the layer is the second of an ffn() whose first left its
+    pre-activation, and dx goes to no sink: the epilogue can apply that activation's derivative."""
+    if pp and trans:
+        return DGRAD_CORE
+    if pp:
+        if PP_DGRAD == "all" or (PP_DGRAD == "fused" and (act_pre or nw > 1)) or _dgrad_shape_on(ws):
+            return DGRAD_CORE_ACT if act_pre else DGRAD_CORE
+        return DGRAD_LIBRARY
+    if trans:
+        return DGRAD_LIBRARY
+    if act_pre and nw == 1:
+        return DGRAD_CORE_ACT if ACT_DGRAD_CORE else DGRAD_HAND_ACT
+    return DGRAD_HAND
+
+
+def _wgrad_first(x, dpre, pp, trans, slots):
+    """The engine that gets a layer's weight (+ bias) gradients first.  ``slots``: every weight and bias of the
+    layer has an fp32 gradient slot (the one-launch engines write nowhere else)."""
+    if (PP_WGRAD == "wg" and not trans and slots and x.dim() == 2 and x.dtype == torch.bfloat16
+            and dpre.dtype == torch.bfloat16 and _wg_ok(x, dpre)):
+        return WGRAD_WG
+    if pp and slots and PP_WGRAD == "all":
+        return WGRAD_CORE
+    return WGRAD_SEGMENTS
+
+
 def _wg_backward(ctx, x, dpre):
     """Weight (+ bias) gradients of a dense layer on the weight-gradient kernel: every segment (q|k|v) in one
     launch straight into the fp32 slots, bias column sums fused (not in deterministic mode: the per-split sums
-    are atomics; a column-sum pass then).  False (nothing done) where the kernel does not apply."""
-    if PP_WGRAD != "wg" or ctx.trans or any(sk is None for sk in ctx.wsinks):
-        return False
-    if ctx.has_b and any(sk is None for sk in ctx.bsinks):
-        return False
-    if not (x.dim() == 2 and x.dtype == torch.bfloat16 and dpre.dtype == torch.bfloat16 and _wg_ok(x, dpre)):
-        return False
+    are atomics; a column-sum pass then).  False (nothing done) where the kernel does not take the shape."""
     fuse_b = ctx.has_b and not N.deterministic()
     # a slot this launch is the step's first writer of is overwritten (V.store_slot: no zero fill, no C read)
     gws, store = zip(*[V.store_slot(sk) for sk in ctx.wsinks])
@@ -432,6 +479,30 @@ class _WeightCats(object):
 _CATS = _WeightCats()
 
 
+def _bias_vector(bs, dtype):
+    """[b_1 | ... | b_n] in the compute dtype: a view where the biases lie back to back, else a copy."""
+    b = bs[0] if len(bs) == 1 else _adjacent(bs)
+    return (b if b is not None else torch.cat(bs, 0)).to(dtype)
+
+
+def _weight_matrix(ws):
+    """[W_1 | ... | W_n] of a forward: the step's cached concatenation where there is one, else a copy."""
+    w = ws[0] if len(ws) == 1 else _CATS.get(ws)
+    return w if w is not None else torch.cat(ws, 1)
+
+
+def _core_fwd(x, ws, bs, act, trans):
+    """(y, pre-activation or None) on the GEMM core; y None where it does not take the shape."""
+    if trans:                                   # x @ w^T, w [N, K]: the dgrad layout
+        y = mm.dgrad(x, ws[0])
+        if y is not None and bs is not None:
+            y.add_(bs[0].to(y.dtype))
+        return y, None
+    pre = torch.empty((x.shape[0], ws[0].shape[1] * len(ws)), dtype=x.dtype, device=x.device) if act == 2 else None
+    bl = [t if t.dtype == x.dtype else t.to(x.dtype) for t in bs] if bs is not None else None
+    return mm.fwd(x, list(ws), biases=bl, act=act, pre=pre), pre
+
+
 class _Dense(torch.autograd.Function):
     """y = act(x @ [W_1 | ... | W_n] + [b_1 | ... | b_n]); ``trans``: W given as [N, K].
 
@@ -444,75 +515,33 @@ class _Dense(torch.autograd.Function):
         tunable.ensure(x.device)
         ws, bs = wb[:nw], wb[nw:]
         has_b = bs[0] is not None
-        ctx.x_sink, ctx.x_shape = x_sink, x_shape
         if x_sink is not None:
             x_sink.register()
-        ctx.pp = False
-        core = PP_FWD == "all" or (PP_FWD == "fused" and (act != 0 or nw > 1)) or (PP_FWD == "act" and act != 0)
-        if not core and PP_FWD_SHAPES and not trans:
-            core = "%dx%d" % (x.shape[1], sum(w.shape[1] for w in ws)) in PP_FWD_SHAPES
-        if PP and (core or PP_FWD != "act") and x.is_cuda and x.dtype == torch.bfloat16 and x.stride(1) == 1 \
-                and N.use_native(x):
-            y = None
-            if not trans and all(w.is_contiguous() and w.dtype == torch.bfloat16 for w in ws):
-                if core:
-                    pre = torch.empty((x.shape[0], ws[0].shape[1] * nw), dtype=x.dtype, device=x.device) \
-                        if act == 2 else None
-                    bl = [t if t.dtype == x.dtype else t.to(x.dtype) for t in bs] if has_b else None
-                    y = mm.fwd(x, list(ws), biases=bl, act=act, pre=pre)
-                    if y is not None:
-                        saved = pre if act == 2 else (y if act == 1 else None)
-                if y is None:                            # hipBLASLt (bias epilogue) + the activation kernel
-                    w = ws[0] if nw == 1 else _CATS.get(ws)
-                    if w is None:
-                        w = torch.cat(ws, 1)
-                    if has_b:
-                        b = bs[0] if nw == 1 else _adjacent(bs)
-                        b = (b if b is not None else torch.cat(bs, 0)).to(x.dtype)
-                        pre = torch.addmm(b, x, w)
-                    else:
-                        pre = torch.mm(x, w)
-                    y = pre if act == 0 else _act_fwd(pre, act)
-                    saved = None if act == 0 else (pre if act == 2 else y)
-            elif trans and nw == 1 and act == 0 and ws[0].is_contiguous() and ws[0].dtype == torch.bfloat16:
-                y = mm.dgrad(x, ws[0]) if PP_FWD == "all" else None     # x @ w^T, w [N, K]: the dgrad layout
-                if y is not None and has_b:
-                    y.add_(bs[0].to(y.dtype))
-                saved = None
-            if y is not None:
-                ctx.pp = True
-                ctx.act, ctx.trans, ctx.nw, ctx.has_b = act, trans, nw, has_b
-                ctx.link_out, ctx.link_in = link_out, link_in
-                if link_out is not None:
-                    link_out.pre, link_out.act, link_out.fused = saved, act, False
-                ctx.widths = [t.shape[0] if trans else t.shape[1] for t in ws]
-                ctx.wsinks = [V.grad_sink(t) for t in ws]
-                ctx.bsinks = [V.grad_sink(t) if t is not None else None for t in bs]
-                ctx.like = wb
-                ctx.save_for_backward(x, saved)
-                return y
-        if has_b:
-            b = bs[0] if nw == 1 else _adjacent(bs)
-            b = (b if b is not None else torch.cat(bs, 0)).to(x.dtype)
-        else:
-            b = None
-        hand = None if trans else hand_fwd(x, ws, b, act)
-        if hand is not None:
-            y, pre = hand
-            saved = pre if act == 2 else (y if act == 1 else None)
-            w = ws[0] if nw == 1 else None          # the data gradient reads the segments in place
-        else:
-            w = ws[0] if nw == 1 else _CATS.get(ws)
-            if w is None:
-                w = torch.cat(ws, 1)
+        route, pp = _fwd_route(x, ws, act, nw, trans)
+        y = w = b = None
+        if route == FWD_CORE:
+            y, pre = _core_fwd(x, ws, bs if has_b else None, act, trans)
+            if y is None:                       # declined; a transposed layer then leaves the core's family
+                route, pp = FWD_LIBRARY, pp and not trans
+        if route == FWD_HAND:                   # (the kernel takes the bias vector: built before the weight matrix)
+            b = _bias_vector(bs, x.dtype) if has_b else None
+            hand = hand_fwd(x, ws, b, act)
+            if hand is None:
+                route = FWD_LIBRARY
+            else:
+                y, pre = hand
+                w = ws[0] if nw == 1 else None  # the data gradient reads the segments in place
+        if route == FWD_LIBRARY:                # hipBLASLt (bias epilogue) + the activation kernel
+            w = _weight_matrix(ws)
             if trans:
                 w = w.t()
+            if has_b and b is None:
+                b = _bias_vector(bs, x.dtype)
             pre = torch.addmm(b, x, w) if has_b else torch.mm(x, w)
-            if act == 0:
-                y, saved = pre, None
-            else:
-                y = _act_fwd(pre, act)
-                saved = pre if act == 2 else y
+            y = pre if act == 0 else _act_fwd(pre, act)
+        saved = pre if act == 2 else (y if act == 1 else None)
+        ctx.pp = pp
+        ctx.x_sink, ctx.x_shape = x_sink, x_shape
         ctx.act, ctx.trans, ctx.nw, ctx.has_b = act, trans, nw, has_b
         ctx.link_out, ctx.link_in = link_out, link_in
         if link_out is not None:
@@ -521,213 +550,166 @@ class _Dense(torch.autograd.Function):
         ctx.wsinks = [V.grad_sink(t) for t in ws]
         ctx.bsinks = [V.grad_sink(t) if t is not None else None for t in bs]
         ctx.like = wb
-        ctx.save_for_backward(x, w, saved)
+        ctx.save_for_backward(x, None if pp else w, saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.pp:
-            return _Dense._backward_pp(ctx, dy)
         x, w, saved = ctx.saved_tensors
-        if w is None:                             # hand-written forward over q|k|v segments
-            w = torch.cat(ctx.like[:ctx.nw], 1)
+        ws, bs = ctx.like[:ctx.nw], ctx.like[ctx.nw:]
+        if not ctx.pp:
+            w = _full_weight(ctx, w, ws)
         dy = dy.contiguous()
         lo = ctx.link_out
-        fused_in = lo is not None and lo.fused          # the consumer's dgrad applied act' already
+        fused_in = lo is not None and lo.fused          # the consumer's data gradient applied act' already
         dpre = dy if (ctx.act == 0 or fused_in) else _act_bwd(dy, saved, ctx.act)
         if lo is not None:
             lo.pre = None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            xs = ctx.x_sink
-            hand = not ctx.trans
-            li = ctx.link_in
-            if xs is None and li is not None and li.pre is not None and hand and ctx.nw == 1:
-                if ACT_DGRAD_CORE:                     # the GEMM core's dgrad with the act-backward epilogue
-                    dx = mm.dgrad(dpre, w, act_pre=li.pre, act_bwd=li.act)
-                else:
-                    dx = hand_dgrad_act(dpre, w, li.pre, li.act)      # ffn(): dx already carries act'(pre)
-                li.fused = dx is not None
-            if dx is None and xs is None:
-                dx = _hand_dgrad(dpre, w) if hand else None
-                if dx is None:
-                    dx = torch.mm(dpre, w.t())
-            elif dx is None:
-                buf, acc = xs.target()
-                if acc:                        # second contribution: C += dpre @ w^T inside the GEMM
-                    b2 = buf.view(-1, w.shape[0])
-                    if not hand or _hand_dgrad(dpre, w, out=b2, accumulate=True) is None:
-                        torch.addmm(b2, dpre, w.t(), out=b2)
-                    xs.written(buf)
-                else:
-                    d2 = _hand_dgrad(dpre, w) if hand else None
-                    xs.written((d2 if d2 is not None else torch.mm(dpre, w.t())).view(ctx.x_shape))
-        ws, bs = ctx.like[:ctx.nw], ctx.like[ctx.nw:]
+        dx = _data_grad(ctx, dpre, w, ws) if ctx.needs_input_grad[0] else None
         with _wgrad_section(ctx, x, dpre):
-            gws, gbs = _Dense._weight_grads(ctx, x, dpre, ws, bs)
+            gws, gbs = _weight_grads(ctx, x, dpre, ws, bs)
         return (dx, None, None, None, None, None, None, None) + tuple(gws) + tuple(gbs)
 
-    @staticmethod
-    def _weight_grads(ctx, x, dpre, ws, bs):
-        if _wg_backward(ctx, x, dpre):
-            return ([V.grad_marker(w) for w in ws],
-                    [V.grad_marker(b) for b in bs] if ctx.has_b else [None] * ctx.nw)
-        gws, gbs = [], []
-        bias_done = [False] * ctx.nw
-        col = 0
-        for j, n in enumerate(ctx.widths):
-            d = dpre[:, col:col + n] if ctx.nw > 1 else dpre
-            col += n
-            sink = ctx.wsinks[j]
-            if sink is not None:
-                if ctx.trans:
-                    _accum_mm(V.accumulate_slot(sink), d.t(), x)
-                else:
-                    bsink = ctx.bsinks[j] if ctx.has_b else None
-                    if wgrad_into(V.accumulate_slot(sink), x, d, V.accumulate_slot(bsink)):
-                        bias_done[j] = True
-                gws.append(V.grad_marker(ws[j]))
-            elif ctx.needs_input_grad[8 + j]:
-                g = torch.mm(d.t(), x) if ctx.trans else torch.mm(x.t(), d)
-                gws.append(g.to(ws[j].dtype))
-            else:
-                gws.append(None)
-        if ctx.has_b and all(bias_done):
-            gbs = [V.grad_marker(b) for b in bs]    # summed inside the weight-gradient kernel
-        elif ctx.has_b:
-            fused = None
-            if ctx.nw > 1 and not any(bias_done) and all(sk is not None for sk in ctx.bsinks):
-                fused = _adjacent([V.accumulate_slot(sk) for sk in ctx.bsinks])     # q|k|v slots back to back
-            if ctx.nw == 1 and ctx.bsinks[0] is not None:
-                kernels.colsum_into(dpre, V.accumulate_slot(ctx.bsinks[0]))
-                gbs.append(V.grad_marker(bs[0]))
-            elif fused is not None:
-                kernels.colsum_into(dpre, fused)
-                gbs = [V.grad_marker(b) for b in bs]
-            else:
-                tot = kernels.colsum(dpre)
-                col = 0
-                for j, n in enumerate(ctx.widths):
-                    part = tot[col:col + n]
-                    col += n
-                    if ctx.bsinks[j] is not None:
-                        if not bias_done[j]:           # (else: summed inside the weight-gradient kernel)
-                            V.accumulate_slot(ctx.bsinks[j]).add_(part)
-                        gbs.append(V.grad_marker(bs[j]))
-                    else:
-                        gbs.append(part.to(bs[j].dtype))
-        else:
-            gbs = [None] * ctx.nw
-        return gws, gbs
+
+def _full_weight(ctx, w, ws):
+    """[K, N] for the library's ``dpre @ W^T``: what the forward saved, else the segments side by side (a layer of
+    the core's family, or a hand-written forward over q|k|v, saved none)."""
+    if w is None:
+        w = ws[0] if ctx.nw == 1 else torch.cat(ws, 1)
+        if ctx.trans:
+            w = w.t()
+    return w
 
 
-def _pp_weight_grads(ctx, x, dpre, ws, bs):
-    """Weight (+ bias) gradients of the core backward, straight into the fp32 slots."""
-    wsinks, bsinks = ctx.wsinks, ctx.bsinks
-    gws, gbs = [None] * ctx.nw, [None] * ctx.nw
-    all_w = all(sk is not None for sk in wsinks)
-    all_b = ctx.has_b and all(sk is not None for sk in bsinks)
-    done = False
-    if _wg_backward(ctx, x, dpre):
-        done = True
-    elif all_w and (all_b or not ctx.has_b) and PP_WGRAD == "all":
-        if ctx.trans:                                   # w [N, K]: g += dy^T x  (C rows = N)
-            done = ctx.nw == 1 and mm.wgrad_into([V.accumulate_slot(wsinks[0])], dpre, x, dbs=None)
-            if done and ctx.has_b:
-                kernels.colsum_into(dpre, V.accumulate_slot(bsinks[0]))
-        else:
-            done = mm.wgrad_into([V.accumulate_slot(sk) for sk in wsinks], x, dpre,
-                                 dbs=[V.accumulate_slot(sk) for sk in bsinks] if ctx.has_b else None)
-    if done:
-        gws = [V.grad_marker(w) for w in ws]
-        if ctx.has_b:
-            gbs = [V.grad_marker(b) for b in bs]
+def _deliver(xs, x_shape, kernel, library):
+    """dx from ``kernel(out, accumulate)``, or where it returns None from ``library(out)``; with a sink ``xs`` it
+    goes there -- a second contribution is accumulated inside the GEMM (C += dpre @ w^T) -- and None is returned."""
+    if xs is None:
+        dx = kernel(None, False)
+        return dx if dx is not None else library(None)
+    buf, acc = xs.target()
+    if acc:
+        b2 = buf.view(-1, x_shape[-1])
+        if kernel(b2, True) is None:
+            library(b2)
+        xs.written(buf)
     else:
-        col = 0
-        for j, n in enumerate(ctx.widths):
-            d = dpre[:, col:col + n] if ctx.nw > 1 else dpre
-            col += n
-            sink = wsinks[j]
-            bias_done = False
-            if sink is not None:
-                if ctx.trans:
-                    _accum_mm(V.accumulate_slot(sink), d.t(), x)
-                else:                                   # conv-kernel wgrad, bias gradient fused in
-                    bsk = bsinks[j] if ctx.has_b else None
-                    bias_done = wgrad_into(V.accumulate_slot(sink), x, d, V.accumulate_slot(bsk))
-                gws[j] = V.grad_marker(ws[j])
-            elif ctx.needs_input_grad[8 + j]:
-                g = torch.mm(d.t(), x) if ctx.trans else torch.mm(x.t(), d)
-                gws[j] = g.to(ws[j].dtype)
-            if ctx.has_b and bias_done:
-                gbs[j] = V.grad_marker(bs[j])
-            elif ctx.has_b and bsinks[j] is not None:
-                slot = V.accumulate_slot(bsinks[j])
-                kernels.colsum_into(d, slot) if d.is_contiguous() else slot.add_(d.float().sum(0))
-                gbs[j] = V.grad_marker(bs[j])
-            elif ctx.has_b:
-                gbs[j] = d.float().sum(0).to(bs[j].dtype)
-    return gws, gbs
+        d2 = kernel(None, False)
+        xs.written((d2 if d2 is not None else library(None)).view(x_shape))
+    return None
 
 
-def _backward_pp(ctx, dy):
-    """Backward of a dense layer on the ping-pong core: no weight concatenation, no bf16 weight gradient,
-    no separate bias column sums or activation-backward pass where the neighbouring GEMM can fold it in."""
-    x, saved = ctx.saved_tensors
-    ws, bs = list(ctx.like[:ctx.nw]), list(ctx.like[ctx.nw:])
-    dy = dy.contiguous()
-    lo = ctx.link_out
-    fused_in = lo is not None and lo.fused          # the consumer's data gradient applied act' already
-    dpre = dy if (ctx.act == 0 or fused_in) else _act_bwd(dy, saved, ctx.act)
-    if lo is not None:
-        lo.pre = None
-    dx = None
-    if ctx.needs_input_grad[0]:
-        xs, li = ctx.x_sink, ctx.link_in
-        if ctx.trans:                                   # y = x w^T (w [N, K]): dx = dy w
-            w = ws[0]
-            dx = mm.fwd(dpre, w) if dpre.shape[1] % 64 == 0 else None
+def _data_grad(ctx, dpre, w, ws):
+    """dx = dpre @ W^T on the engine ``_dgrad_route`` names (None once it is in the input's sink).  No weight
+    concatenation and no activation-backward pass where the GEMM can read segments / fold the derivative in."""
+    xs, li = ctx.x_sink, ctx.link_in
+    ap = li.pre if (li is not None and xs is None) else None
+    route = _dgrad_route(ctx.pp, ws, ctx.nw, ctx.trans, ap is not None, xs is not None)
+    fused = route in (DGRAD_CORE_ACT, DGRAD_HAND_ACT)       # ffn(): dx already carries act'(pre)
+
+    def library(out):
+        wt = _full_weight(ctx, w, ws).t()
+        return torch.addmm(out, dpre, wt, out=out) if out is not None else torch.mm(dpre, wt)
+
+    def kernel(out, accumulate):
+        if ctx.pp and ctx.trans:                # y = x w^T (w [N, K]): dx = dy w, the core's forward layout
+            dx = mm.fwd(dpre, ws[0]) if dpre.shape[1] % 64 == 0 else None
             if dx is None:
-                dx = torch.mm(dpre, w)
-            if xs is not None:
-                buf, acc = xs.target()
-                if acc:
-                    buf.view(-1, dx.shape[1]).add_(dx)
-                    xs.written(buf)
-                else:
-                    xs.written(dx.view(ctx.x_shape))
-                dx = None
-        elif xs is None:
-            ap = li.pre if (li is not None and li.pre is not None) else None
-            core = PP_DGRAD == "all" or (PP_DGRAD == "fused" and (ap is not None or ctx.nw > 1)) or \
-                _dgrad_shape_on(ws)
-            dx = mm.dgrad(dpre, ws, act_pre=ap, act_bwd=li.act if ap is not None else 0) if core else None
-            if dx is not None and ap is not None:
-                li.fused = True
-            if dx is None:
-                w = ws[0] if ctx.nw == 1 else torch.cat(ws, 1)
-                dx = torch.mm(dpre, w.t())
+                dx = library(None)
+            return out.add_(dx) if accumulate else dx
+        dx = None
+        if route == DGRAD_HAND_ACT:
+            dx = hand_dgrad_act(dpre, w, ap, li.act)
+        elif route in (DGRAD_CORE, DGRAD_CORE_ACT):
+            dx = mm.dgrad(dpre, ws, out=out, accumulate=accumulate, act_pre=ap if fused else None,
+                          act_bwd=li.act if fused else 0)
+        if fused:
+            li.fused = dx is not None
+        if dx is None and not ctx.pp and route != DGRAD_LIBRARY:
+            dx = _hand_dgrad(dpre, w, out=out, accumulate=accumulate)
+        return dx
+    return _deliver(xs, ctx.x_shape, kernel, library)
+
+
+def _core_wgrad(ctx, x, dpre):
+    """Every weight (+ bias) gradient of the layer in one launch of the GEMM core; False where it declines."""
+    wsinks, bsinks = ctx.wsinks, ctx.bsinks
+    if ctx.trans:                                   # w [N, K]: g += dy^T x  (C rows = N)
+        done = ctx.nw == 1 and mm.wgrad_into([V.accumulate_slot(wsinks[0])], dpre, x, dbs=None)
+        if done and ctx.has_b:
+            kernels.colsum_into(dpre, V.accumulate_slot(bsinks[0]))
+        return done
+    return mm.wgrad_into([V.accumulate_slot(sk) for sk in wsinks], x, dpre,
+                         dbs=[V.accumulate_slot(sk) for sk in bsinks] if ctx.has_b else None)
+
+
+def _segment_bias_grad(ctx, d, j, b):
+    """The core family's bias tail, segment by segment as the weight loop goes: a column sum of the segment."""
+    if ctx.bsinks[j] is None:
+        return d.float().sum(0).to(b.dtype)
+    slot = V.accumulate_slot(ctx.bsinks[j])
+    kernels.colsum_into(d, slot) if d.is_contiguous() else slot.add_(d.float().sum(0))
+    return V.grad_marker(b)
+
+
+def _layer_bias_grads(ctx, dpre, bs, bias_done):
+    """The other layers' bias tail, after the weight loop: ONE column sum over the whole ``dpre`` (q|k|v slots
+    that lie back to back take it in place), split where some segment still needs its part."""
+    if ctx.nw == 1 and ctx.bsinks[0] is not None:
+        kernels.colsum_into(dpre, V.accumulate_slot(ctx.bsinks[0]))
+        return [V.grad_marker(bs[0])]
+    if ctx.nw > 1 and not any(bias_done) and all(sk is not None for sk in ctx.bsinks):
+        fused = _adjacent([V.accumulate_slot(sk) for sk in ctx.bsinks])     # q|k|v slots back to back
+        if fused is not None:
+            kernels.colsum_into(dpre, fused)
+            return [V.grad_marker(b) for b in bs]
+    gbs = []
+    tot = kernels.colsum(dpre)
+    col = 0
+    for j, n in enumerate(ctx.widths):
+        part = tot[col:col + n]
+        col += n
+        if ctx.bsinks[j] is not None:
+            if not bias_done[j]:           # (else: summed inside the weight-gradient kernel)
+                V.accumulate_slot(ctx.bsinks[j]).add_(part)
+            gbs.append(V.grad_marker(bs[j]))
         else:
-            buf, acc = xs.target()
-            K = ws[0].shape[0]
-            core = PP_DGRAD == "all" or (PP_DGRAD == "fused" and ctx.nw > 1) or _dgrad_shape_on(ws)
-            if acc:                                     # second contribution: C += dpre @ w^T inside the GEMM
-                b2 = buf.view(-1, K)
-                if not core or mm.dgrad(dpre, ws, out=b2, accumulate=True) is None:
-                    torch.addmm(b2, dpre, torch.cat(ws, 1).t() if ctx.nw > 1 else ws[0].t(), out=b2)
-                xs.written(buf)
-            else:
-                d2 = mm.dgrad(dpre, ws) if core else None
-                if d2 is None:
-                    d2 = torch.mm(dpre, torch.cat(ws, 1).t() if ctx.nw > 1 else ws[0].t())
-                xs.written(d2.view(ctx.x_shape))
-    # weight (+ bias) gradients straight into the fp32 slots
-    with _wgrad_section(ctx, x, dpre):
-        gws, gbs = _pp_weight_grads(ctx, x, dpre, ws, bs)
-    return (dx, None, None, None, None, None, None, None) + tuple(gws) + tuple(gbs)
+            gbs.append(part.to(bs[j].dtype))
+    return gbs
 
 
-_Dense._backward_pp = staticmethod(_backward_pp)
+def _weight_grads(ctx, x, dpre, ws, bs):
+    """Weight (+ bias) gradients, straight into the fp32 slots where the variables have them: in one launch on
+    the engine ``_wgrad_first`` names, else segment by segment."""
+    slots = all(sk is not None for sk in ctx.wsinks) and (not ctx.has_b or all(sk is not None for sk in ctx.bsinks))
+    first = _wgrad_first(x, dpre, ctx.pp, ctx.trans, slots)
+    if (first == WGRAD_WG and _wg_backward(ctx, x, dpre)) or (first == WGRAD_CORE and _core_wgrad(ctx, x, dpre)):
+        return [V.grad_marker(w) for w in ws], [V.grad_marker(b) for b in bs] if ctx.has_b else [None] * ctx.nw
+    gws, gbs, bias_done = [], [None] * ctx.nw, []
+    col = 0
+    for j, n in enumerate(ctx.widths):
+        d = dpre[:, col:col + n] if ctx.nw > 1 else dpre
+        col += n
+        sink = ctx.wsinks[j]
+        bias_done.append(False)
+        if sink is not None:
+            if ctx.trans:
+                _accum_mm(V.accumulate_slot(sink), d.t(), x)
+            else:                                   # conv-kernel wgrad, bias gradient fused in
+                bsink = ctx.bsinks[j] if ctx.has_b else None
+                bias_done[j] = wgrad_into(V.accumulate_slot(sink), x, d, V.accumulate_slot(bsink))
+            gws.append(V.grad_marker(ws[j]))
+        elif ctx.needs_input_grad[8 + j]:
+            g = torch.mm(d.t(), x) if ctx.trans else torch.mm(x.t(), d)
+            gws.append(g.to(ws[j].dtype))
+        else:
+            gws.append(None)
+        if ctx.has_b and ctx.pp:
+            gbs[j] = V.grad_marker(bs[j]) if bias_done[j] else _segment_bias_grad(ctx, d, j, bs[j])
+    if ctx.has_b and not ctx.pp:
+        # the two families' bias tails stay apart: they sum in different orders (per segment / over the layer)
+        gbs = [V.grad_marker(b) for b in bs] if all(bias_done) else _layer_bias_grads(ctx, dpre, bs, bias_done)
+    return gws, gbs
 
 
 def matmul(a, b):
