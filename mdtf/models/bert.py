@@ -71,7 +71,7 @@ def _dropout(x, rate):
 
 class Bert(Model):
     def __init__(self, size="base", vocab_size=30522, max_position=512, type_vocab=2, max_predictions=20,
-                 seq_len=128, dropout=0.1):
+                 seq_len=128, dropout=0.1, causal=False):
         cfg = CONFIGS[size]
         self.H = cfg["hidden"]
         self.L = cfg["layers"]
@@ -83,6 +83,7 @@ class Bert(Model):
         self.P = max_predictions
         self.S = seq_len
         self.dropout = dropout
+        self.causal = causal      # left-to-right encoder: token i attends to tokens <= i
 
     def unpack(self, raw):
         S_, P = self.S, self.P
@@ -155,7 +156,7 @@ class Bert(Model):
                 qkv = ops.dense_multi(x, [ws[n] for n in order], [bs[n] for n in order])   # one GEMM
                 qkv = qkv.reshape(-1, 3 * H)
                 drop = self.dropout if S.is_training() else 0.0
-                ctx = T.fused_attention(qkv, B, S_, nh, amask, drop).reshape(B, S_, H)
+                ctx = T.fused_attention(qkv, B, S_, nh, amask, drop, causal=self.causal).reshape(B, S_, H)
             with V.variable_scope("output"):
                 a = _dense("dense", ctx, H)
                 x = _ln("LayerNorm", a, residual=x, dropout=self.dropout)

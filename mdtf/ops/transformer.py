@@ -306,15 +306,25 @@ def bert_embeddings(word, pos, typ, ids, types):
     return e + embedding_lookup(pos, pos_ids) + embedding_lookup(typ, types)
 
 
-def attention(q, k, v, mask=None, dropout=0.0):
+def attention(q, k, v, mask=None, dropout=0.0, causal=False):
     """Multi-head attention core: q, k, v [B, heads, S, d] -> [B, heads, S, d].
 
     Unfused path: two batched GEMMs (hipBLASLt on the GPU) around the scaled
     masked softmax kernel; attention-probability dropout as in TF BERT.
+    ``causal``: query q sees keys <= q only.  That softmax is computed in fp32 with PyTorch ops (the masked
+    softmax kernel broadcasts one mask row per batch item and cannot take a per-query mask).
     """
     scale = 1.0 / math.sqrt(q.shape[-1])
     scores = torch.matmul(q, k.transpose(-1, -2))
-    p = masked_softmax(scores, mask, scale)
+    if causal:
+        s = scores.float() * scale
+        if mask is not None:
+            s = s + mask.float()[:, None, None, :]
+        S_ = s.shape[-1]
+        tri = torch.full((S_, S_), float("-inf"), device=s.device).triu(1)     # 0 on and below the diagonal
+        p = torch.softmax(s + tri, -1).to(scores.dtype)
+    else:
+        p = masked_softmax(scores, mask, scale)
     if dropout:
         p = F.dropout(p, dropout, True)
     return torch.matmul(p, v)
@@ -372,7 +382,45 @@ class _FusedAttention(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None
 
 
-def fused_attention(qkv, batch, seq, heads, mask=None, dropout=0.0):
+N.register("mdtf_attn_fwd_causal", [N.P, N.P, N.P, N.P, N.I, N.I, N.I, N.I, N.F, N.F, N.U, N.P, N.P])
+N.register("mdtf_attn_bwd_causal", [N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.I, N.I, N.I, N.I, N.F, N.F, N.U, N.P, N.P])
+
+
+class _CausalAttention(torch.autograd.Function):
+    """softmax(Q K^T / sqrt(d) + mask + causal triangle) V for all heads, straight from/to the fused QKV layout
+    (``csrc/attention_causal.hip``: any S % 64 == 0, head dim 64 / 128)."""
+
+    @staticmethod
+    def forward(ctx, qkv, mask, B, S_, nh, p_drop, seed):
+        qkv = qkv.contiguous()
+        dh = qkv.shape[-1] // 3 // nh
+        out = torch.empty((B * S_, nh * dh), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B * nh, S_), dtype=torch.float32, device=qkv.device)
+        m = mask.float().contiguous() if mask is not None else None
+        scale = 1.0 / math.sqrt(dh)
+        N.check(N.fn("mdtf_attn_fwd_causal")(N.ptr(qkv), N.ptr(m), N.ptr(out), N.ptr(lse), B, S_, nh, dh, scale,
+                                             float(p_drop), seed, N.ptr(_seed_off(p_drop, qkv.device)),
+                                             N.stream_ptr()), "attn_fwd_causal")
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.mask = m
+        ctx.args = (B, S_, nh, float(p_drop), seed, scale, dh)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        B, S_, nh, p_drop, seed, scale, dh = ctx.args
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        ws = torch.empty((B * nh * S_,), dtype=torch.float32, device=qkv.device)
+        N.check(N.fn("mdtf_attn_bwd_causal")(N.ptr(qkv), N.ptr(ctx.mask), N.ptr(out), N.ptr(dout), N.ptr(lse),
+                                             N.ptr(dqkv), N.ptr(ws), B, S_, nh, dh, scale, p_drop, seed,
+                                             N.ptr(_seed_off(p_drop, qkv.device)), N.stream_ptr()),
+                "attn_bwd_causal")
+        return dqkv, None, None, None, None, None, None
+
+
+def fused_attention(qkv, batch, seq, heads, mask=None, dropout=0.0, causal=False):
     """Self-attention from the fused projection ``qkv`` [B*S, 3H] (q | k | v, heads
     contiguous inside each) to the context [B*S, H].
 
@@ -381,10 +429,20 @@ def fused_attention(qkv, batch, seq, heads, mask=None, dropout=0.0):
     the tiled online-softmax kernels (``csrc/attention_flash.hip``); otherwise the unfused
     matmul/softmax path.
     ``mask``: additive [B, S] key mask (0 keep, -10000 drop) or None.
+    ``causal``: query q attends to keys <= q only (left-to-right models).  GPU, bf16, S % 64 == 0 (S = 128
+    included), head dim 64 / 128: the triangle-aware tiled kernels (``csrc/attention_causal.hip``); otherwise
+    the unfused path with the fp32 PyTorch softmax of ``attention``.
     """
     H3 = qkv.shape[-1]
     H = H3 // 3
     dh = H // heads
+    if causal:
+        if N.use_native(qkv) and qkv.dtype == torch.bfloat16 and flash_ok(seq, dh):
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout else 0
+            return _CausalAttention.apply(qkv.reshape(batch * seq, H3), mask, batch, seq, heads, float(dropout), seed)
+        q, k, v = qkv.reshape(batch, seq, 3, heads, dh).unbind(2)
+        ctx = attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), mask, dropout, causal=True)
+        return ctx.transpose(1, 2).reshape(batch * seq, H)
     if N.use_native(qkv) and qkv.dtype == torch.bfloat16 and ((seq == FUSED_SEQ and dh == FUSED_DIM)
                                                               or flash_ok(seq, dh)):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout else 0
