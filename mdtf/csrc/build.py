@@ -27,7 +27,8 @@ HIP_FLAGS = ["-O3", "-std=c++17", "--offload-arch=%s" % ARCH, "-fPIC", "-munsafe
 # (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); attention_causal.hip is the first.  With the flag its code object
 # holds none of them, without it 234 (profiles/attention_causal.md, "Registers").  The older sources keep their
 # flags, and so their code, unchanged.
-HIP_EXTRA_FLAGS = {"attention_causal.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_EXTRA_FLAGS = {"attention_causal.hip": _NO_PACKED_FP32, "conv_group.hip": _NO_PACKED_FP32}
 HOST_FLAGS = ["-O3", "-std=c++17", "-msse4.2", "-fPIC", "-pthread", "-Wall", "-Wno-unused-result"]
 
 

@@ -218,36 +218,42 @@ def bias(bias_shape):
 
 
 def conv_bn(layer_name, x, out_channels, kernel_size=3, stride=1, relu=True, residual=None, training=True,
-            bn_decay=0.9, bn_epsilon=1e-5, zero_gamma=False, padding=None, defer=False, pool=None, on_consumer=False):
+            bn_decay=0.9, bn_epsilon=1e-5, zero_gamma=False, padding=None, defer=False, pool=None, on_consumer=False,
+            groups=1):
     """conv (no bias) → BN (→ +residual) (→ ReLU), ResNet v1.5 building unit.
 
     Stride>1 convs use TF-official "fixed padding" (symmetric ``(k-1)//2``).  ``defer``: the BN may be
     returned unapplied (``ops.bn.DeferredBN``) for the residual BN that adds it to apply (GPU training).
     ``pool = (ksize, stride, padding)``: a max pool after the ReLU (fused with the BN on the GPU).
     ``on_consumer``: the output's only reader is a 1x1 conv, which may apply the BN + ReLU itself (GPU training).
+    ``groups`` above 1: a grouped conv with the filter ``[k, k, Cin / groups, Cout]`` (fan-in from ``Cin / groups``),
+    followed by the BN on its own statistics pass; ``defer`` and ``on_consumer`` are ignored.
     """
-    variables = conv_bn_variables(layer_name, x, out_channels, kernel_size, zero_gamma=zero_gamma)
+    variables = conv_bn_variables(layer_name, x, out_channels, kernel_size, zero_gamma=zero_gamma, groups=groups)
     return conv_bn_apply(x, variables, kernel_size, stride, relu, residual, training, bn_decay, bn_epsilon, padding,
-                         defer, pool, on_consumer)
+                         defer, pool, on_consumer, groups)
 
 
 def conv_bn_apply(x, variables, kernel_size=3, stride=1, relu=True, residual=None, training=True, bn_decay=0.9,
-                  bn_epsilon=1e-5, padding=None, defer=False, pool=None, on_consumer=False):
+                  bn_epsilon=1e-5, padding=None, defer=False, pool=None, on_consumer=False, groups=1):
     """:func:`conv_bn` on variables already made by :func:`conv_bn_variables`."""
     k = kernel_size
     if padding is None:
         padding = "SAME" if stride == 1 else ((k - 1) // 2, (k - 1) // 2)
     w, gamma, beta, mm, mv = variables
     return ops.conv_bn(x, w, gamma, beta, mm, mv, stride, padding, training, bn_decay, bn_epsilon, relu, residual,
-                       defer=defer, pool=pool, on_consumer=on_consumer)
+                       defer=defer, pool=pool, on_consumer=on_consumer, groups=groups)
 
 
-def conv_bn_variables(layer_name, x, out_channels, kernel_size=3, zero_gamma=False, **unused):
-    """The variables of :func:`conv_bn` (created on first use, reused after): weights, gamma, beta, moving
-    mean / variance."""
+def conv_bn_variables(layer_name, x, out_channels, kernel_size=3, zero_gamma=False, groups=1, **unused):
+    """The variables of :func:`conv_bn` (created on first use, reused after): weights ``[k, k, Cin / groups, Cout]``,
+    gamma, beta, moving mean / variance."""
     k = kernel_size
+    if x.shape[-1] % groups or out_channels % groups:
+        raise ValueError("conv_bn: groups=%d must divide %d and %d channels" % (groups, x.shape[-1], out_channels))
     with V.variable_scope(layer_name):
-        w = V.get_variable('weights', [k, k, x.shape[-1], out_channels], initializer=V.variance_scaling_initializer())
+        w = V.get_variable('weights', [k, k, x.shape[-1] // groups, out_channels],
+                           initializer=V.variance_scaling_initializer())
         c = out_channels
         gamma = V.get_variable('BatchNorm/gamma', [c], initializer=V.constant_initializer(0.0 if zero_gamma else 1.0),
                                keep_fp32=True)

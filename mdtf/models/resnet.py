@@ -30,9 +30,14 @@ PROJ_LATE = os.environ.get("MDTF_PROJ_LATE", "0") == "1"
 
 class ResNet(Model):
     def __init__(self, depth=50, num_classes=1000, zero_init_residual=True, bn_decay=0.9, bn_epsilon=1e-5,
-                 width=64):
+                 width=64, cardinality=1, base_width=64):
+        """``cardinality`` / ``base_width``: ResNeXt (Xie et al. 2017).  conv1 / conv2 of a bottleneck are
+        ``filters * base_width // 64 * cardinality`` wide and conv2 is a grouped conv of ``cardinality`` groups;
+        conv3 and the shortcut are unchanged.  The defaults are the plain ResNet."""
         if DEPTHS.get(depth) is None:
             raise ValueError("unsupported ResNet depth %d" % depth)
+        self.cardinality = cardinality
+        self.base_width = base_width
         self.depth = depth
         self.blocks = DEPTHS[depth]
         self.num_classes = num_classes
@@ -55,9 +60,10 @@ class ResNet(Model):
                 # gradient is the first contribution to x's gradient and can be deferred into conv1's
                 # (ops.actsink, one fused pass over the block input's gradient)
                 sc_vars = tools.conv_bn_variables("shortcut", x, 4 * filters, 1, **kw)
-            y = tools.conv_bn("conv1", x, filters, 1, 1, relu=True, **kw)
+            inner = filters * self.base_width // 64 * self.cardinality
+            y = tools.conv_bn("conv1", x, inner, 1, 1, relu=True, **kw)
             # (conv3 is its output's only reader: it may apply this BN + ReLU to its operand, ops.bn ON_CONSUMER)
-            y = tools.conv_bn("conv2", y, filters, 3, stride, relu=True, on_consumer=True, **kw)
+            y = tools.conv_bn("conv2", y, inner, 3, stride, relu=True, on_consumer=True, groups=self.cardinality, **kw)
             if proj and PROJ_LATE:
                 shortcut = tools.conv_bn_apply(x, sc_vars, 1, stride, relu=False, defer=True, **kw)
             elif not proj:
@@ -96,6 +102,23 @@ class ResNet50(ResNet):
 class ResNet152(ResNet):
     def __init__(self, **kw):
         super(ResNet152, self).__init__(152, **kw)
+
+
+class ResNeXt50_32x4d(ResNet):
+    """ResNeXt-50 32x4d: grouped 3x3 convs of 4, 8, 16 and 32 channels per group (``ops/grouped.py``)."""
+
+    def __init__(self, **kw):
+        super(ResNeXt50_32x4d, self).__init__(50, cardinality=32, base_width=4, **kw)
+        self.name = "resnext_50_32x4d"
+
+
+class ResNeXt101_32x8d(ResNet):
+    """ResNeXt-101 32x8d: 8, 16, 32 and 64 channels per group; the last stage's 64-wide groups run the library's
+    grouped conv until the kernels take them."""
+
+    def __init__(self, **kw):
+        super(ResNeXt101_32x8d, self).__init__(101, cardinality=32, base_width=8, **kw)
+        self.name = "resnext_101_32x8d"
 
 
 class SoftmaxCrossEntropyLoss(Loss):

@@ -62,20 +62,36 @@ def _torch_conv_nhwc(x, w_hwio, sh, sw, pads, dh, dw, groups=1):
     return y.permute(0, 2, 3, 1)
 
 
-def conv2d(x, w, strides=1, padding="SAME", dilations=1, bias=None, act=None, name=None):
+def conv2d(x, w, strides=1, padding="SAME", dilations=1, bias=None, act=None, name=None, groups=1):
     """2-D convolution, NHWC input, HWIO filter (``tf.nn.conv2d``).
 
     ``strides``/``dilations`` accept an int, ``[sh, sw]`` or TF's ``[1, sh, sw, 1]``.
     ``padding`` is 'SAME', 'VALID', an int, ``(ph, pw)`` or ``(pt, pb, pl, pr)``.
     Optional fused epilogue: ``bias`` (per output channel) and ``act='relu'``.
+    ``groups`` above 1: a grouped convolution with the filter ``[kh, kw, C / groups, Cout]`` (Keras
+    ``Conv2D(groups=...)``): output channel ``co`` belongs to group ``co // (Cout / groups)`` and reads that group's
+    ``C / groups`` input channels.  bf16 GPU tensors with ``C == Cout``, ``C % 32 == 0``, 4, 8, 16 or 32 channels per
+    group, a 3x3 filter, stride 1 or 2 and dilation 1 run the HIP kernels of ``ops/grouped.py``; every other grouped
+    call runs the PyTorch expression.  ``bias`` / ``act`` are applied after a grouped conv by their own ops.
     """
     n, h, wd, c = x.shape
     kh, kw, ci, co = w.shape
-    if ci != c:
-        raise ValueError("conv2d: input has %d channels, filter expects %d" % (c, ci))
+    if groups < 1 or c % groups or co % groups:
+        raise ValueError("conv2d: groups=%d must divide the %d input and %d output channels" % (groups, c, co))
+    if ci * groups != c:
+        raise ValueError("conv2d: input has %d channels, filter expects %d" % (c, ci * groups))
     sh, sw = pair(strides)
     dh, dw = pair(dilations)
     oh, ow, pt, pb, pl, pr = conv_geometry(h, wd, kh, kw, (sh, sw), padding, (dh, dw))
+    if groups > 1:
+        from . import grouped
+        if grouped.native_ok(x, w, groups, (sh, sw), (dh, dw), (pt, pb, pl, pr)):
+            y = grouped.grouped_nhwc(x, w, sh, (pt, pb, pl, pr), (oh, ow))
+        else:
+            y = _torch_conv_nhwc(x, w, sh, sw, (pt, pb, pl, pr), dh, dw, groups=groups)
+        if bias is not None:
+            y = bias_add(y, bias)
+        return relu(y) if act == "relu" else y
     if _native.use_native(x):
         from . import conv as conv_mod
         return conv_mod.conv2d_nhwc(x, w, (sh, sw), (pt, pb, pl, pr), (dh, dw), bias=bias, act=act)
@@ -276,7 +292,7 @@ def batch_norm(x, gamma, beta, moving_mean, moving_var, training=True, decay=0.9
 
 
 def conv_bn(x, w, gamma, beta, moving_mean, moving_var, strides=1, padding="SAME", training=True, decay=0.9,
-            epsilon=1e-5, relu=True, residual=None, defer=False, pool=None, on_consumer=False):
+            epsilon=1e-5, relu=True, residual=None, defer=False, pool=None, on_consumer=False, groups=1):
     """conv2d (no bias) -> batch_norm (+residual) (+ReLU).
 
     On the GPU the conv epilogue emits the per-channel Σy/Σy² partials, so the
@@ -287,11 +303,17 @@ def conv_bn(x, w, gamma, beta, moving_mean, moving_var, strides=1, padding="SAME
     as one pass (``bn.bn_relu_maxpool_nhwc``).
     ``on_consumer``: the output feeds only a 1x1 conv that may apply the BN + ReLU to its operand on the GPU
     (``bn.ON_CONSUMER``).
+    ``groups`` above 1: the grouped :func:`conv2d`, then :func:`batch_norm` with its own statistics pass (the grouped
+    kernels have no statistics epilogue); ``defer`` and ``on_consumer`` are ignored.
     """
     n, h, wd, c = x.shape
     kh, kw, ci, co = w.shape
     sh, sw = pair(strides)
     oh, ow, pt, pb, pl, pr = conv_geometry(h, wd, kh, kw, (sh, sw), padding)
+    if groups > 1:
+        y = conv2d(x, w, strides, (pt, pb, pl, pr), groups=groups)
+        y = batch_norm(y, gamma, beta, moving_mean, moving_var, training, decay, epsilon, relu, residual)
+        return y if pool is None else max_pool(y, pool[0], pool[1], pool[2])
     if _native.use_native(x) and training:
         from . import conv as conv_mod
         from . import bn
