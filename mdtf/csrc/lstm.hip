@@ -1,0 +1,322 @@
+// LSTM recurrence (TF LSTMCell / BasicLSTMCell, gate order i, j, f, o) for gfx950: one launch per time step, the
+// whole cell update in the epilogue of a skinny MFMA GEMM.  bf16 activations and weights, fp32 accumulation and cell
+// state.  ops/rnn.py is the caller; the input half (x @ kernel[:I] + bias over all T * B rows), the weight gradients
+// and dx are ordinary GEMMs and stay on the dense routes.
+//
+//   [i j f o] = xg_t + h_{t-1} @ kernel[I:]                       kernel [I + H, 4H]
+//   c_t = c_{t-1} * sigmoid(f + forget_bias) + sigmoid(i) * tanh(j)
+//   h_t = tanh(c_t) * sigmoid(o)
+//
+// Work split.  A block owns U hidden units (16 or 32) of one 16-row batch tile and computes the four gate strips of
+// those units, so a lane's accumulators hold i, j, f, o of the same (row, unit) in matching slots and the cell update
+// needs no exchange between gates.  The batch is small (16..256 rows), so the tiles are small and K is split over the
+// block's four waves in interleaved 32-wide steps; the four partial tiles meet in LDS and are summed in wave order
+// (fixed, so bitwise repeatable).  Each wave then runs the epilogue of a quarter of the tile's rows.
+//
+// Operands.  Both MFMA operands are 16-byte K-contiguous vectors loaded straight into VGPRs through a two-slot
+// register ring (the load of step s + 2 is issued when step s is consumed): h_{t-1} is K-contiguous as it is, and
+// lstm_pack_w repacks kernel[I:] once per forward call into wt[H / U][4][U][H], the four gate strips of a unit slice
+// adjacent.  The backward's prologue GEMM dG_{t+1} @ kernel[I + slice, :]^T (K = 4H) reads both operands in their
+// natural layouts.  No LDS staging, no transposed reads.
+//
+// No kernel spans time steps, no block waits for another, no float atomics: every (row, unit) of the state and of the
+// carried cell gradient has exactly one owner lane in exactly one block per launch.
+#include "mdtf_common.h"
+
+using namespace mdtf;
+
+namespace {
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+constexpr int kRows = 16;      // batch rows per block (one MFMA tile)
+constexpr int kWaves = 4;      // K is split over the waves of a block
+constexpr int kRing = 2;       // register load ring depth, in k-steps of one wave
+constexpr int kStep = 32;      // K per MFMA
+
+__device__ __forceinline__ float rcp_fast(float v) { return __builtin_amdgcn_rcpf(v); }
+__device__ __forceinline__ float sigmoid_fast(float v) { return rcp_fast(1.0f + __expf(-v)); }
+// 2 sigmoid(2v) - 1; the exponent saturates to inf / 0 at both ends, which gives -1 / 1
+__device__ __forceinline__ float tanh_fast(float v) { return 2.0f * rcp_fast(1.0f + __expf(-2.0f * v)) - 1.0f; }
+
+__device__ __forceinline__ bf16x8_t load_frag(const bf16_t* p, bool ok) {
+  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+  if (ok) raw = *reinterpret_cast<const uint4*>(p);
+  return __builtin_bit_cast(bf16x8_t, raw);
+}
+
+// acc[s] (16 rows x 16 columns, this wave's share of K) for NB column strips: rows `arow`-relative of A [.., lda]
+// against the strips Bm + s * 16 * ldb, each 16 rows of a K-contiguous [.., ldb] matrix.  Lane l holds row / column
+// l % 16 and the k-octet l / 16 of each 32-wide step; a row at or past `a_ok` is read as zeros.
+template <int NB>
+__device__ __forceinline__ void skinny_gemm(const bf16_t* __restrict__ a_lane, bool a_ok,
+                                            const bf16_t* __restrict__ b_lane, int64_t strip, int nsteps, int wave,
+                                            float4v (&acc)[NB]) {
+  bf16x8_t ra[kRing], rb[kRing][NB];
+#pragma unroll
+  for (int d = 0; d < kRing; ++d) {
+    const int s = wave + d * kWaves;
+    if (s < nsteps) {
+      ra[d] = load_frag(a_lane + s * kStep, a_ok);
+#pragma unroll
+      for (int n = 0; n < NB; ++n) rb[d][n] = load_frag(b_lane + n * strip + s * kStep, true);
+    }
+  }
+  for (int s0 = wave; s0 < nsteps; s0 += kRing * kWaves) {
+#pragma unroll
+    for (int d = 0; d < kRing; ++d) {
+      const int s = s0 + d * kWaves;
+      if (s < nsteps) {
+        const bf16x8_t fa = ra[d];
+        bf16x8_t fb[NB];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) fb[n] = rb[d][n];
+        const int nx = s + kRing * kWaves;           // refill the slot just read
+        if (nx < nsteps) {
+          ra[d] = load_frag(a_lane + nx * kStep, a_ok);
+#pragma unroll
+          for (int n = 0; n < NB; ++n) rb[d][n] = load_frag(b_lane + n * strip + nx * kStep, true);
+        }
+#pragma unroll
+        for (int n = 0; n < NB; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[n], acc[n], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The four waves' partial tiles -> LDS -> this wave's quarter, summed in wave order.  red: [kWaves][NB][4][64] floats.
+// Wave w ends up with out[n] = the sum of accumulator slot j = w of strip n (row (l / 16) * 4 + w, column l % 16).
+template <int NB>
+__device__ __forceinline__ void reduce_waves(float* red, const float4v (&acc)[NB], int wave, int lane,
+                                             float (&out)[NB]) {
+#pragma unroll
+  for (int n = 0; n < NB; ++n)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[((wave * NB + n) * 4 + j) * kWave + lane] = acc[n][j];
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < NB; ++n) {
+    float v = red[((0 * NB + n) * 4 + wave) * kWave + lane];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) v += red[((w * NB + n) * 4 + wave) * kWave + lane];
+    out[n] = v;
+  }
+}
+
+// kernel[I:] ([H, 4H], k-major) -> wt[H / U][4][U][H] (K-contiguous): 32 x 32 tiles through LDS, both sides coalesced
+__global__ __launch_bounds__(256) void lstm_pack_w(const bf16_t* __restrict__ wh, bf16_t* __restrict__ wt, int H,
+                                                   int U) {
+  __shared__ bf16_t tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int k0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) tile[ty + 8 * r][tx] = wh[static_cast<int64_t>(k0 + ty + 8 * r) * (4 * H) + n0 + tx];
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int col = n0 + ty + 8 * r;
+    const int g = col / H, unit = col - g * H;
+    const int s = unit / U, u = unit - s * U;
+    wt[(static_cast<int64_t>(s * 4 + g) * U + u) * H + k0 + tx] = tile[tx][ty + 8 * r];
+  }
+}
+
+struct FwdArgs {
+  const bf16_t* xg;      // [B, 4H] of this step
+  const bf16_t* wt;      // packed recurrent weights
+  const bf16_t* h_prev;  // [B, H]
+  const float* c_prev;   // [B, H]
+  bf16_t* h;             // [B, H]
+  float* c;              // [B, H]
+  bf16_t* gates;         // [B, 4H], post-activation i, j, f, o
+  int B, H;
+  float forget_bias;
+};
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void lstm_step_fwd(FwdArgs a) {
+  constexpr int NT = U / 16, NB = 4 * NT;          // strip g * NT + nt: gate g, units nt * 16 .. + 15 of the slice
+  __shared__ float red[kWaves * NB * 4 * kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+
+  float4v acc[NB];
+#pragma unroll
+  for (int n = 0; n < NB; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+  const int arow = row0 + lr;
+  const bool a_ok = arow < a.B;
+  const bf16_t* a_lane = a.h_prev + static_cast<int64_t>(a_ok ? arow : 0) * H + lk;
+  const bf16_t* b_lane = a.wt + (static_cast<int64_t>(slice) * 4 * U + lr) * H + lk;
+  skinny_gemm<NB>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * H, H / kStep, wave, acc);
+
+  float pre[NB];
+  reduce_waves<NB>(red, acc, wave, lane, pre);
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 4 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    const float pi = pre[0 * NT + nt] + bf2f(a.xg[g0]);
+    const float pj = pre[1 * NT + nt] + bf2f(a.xg[g0 + H]);
+    const float pf = pre[2 * NT + nt] + bf2f(a.xg[g0 + 2 * H]) + a.forget_bias;
+    const float po = pre[3 * NT + nt] + bf2f(a.xg[g0 + 3 * H]);
+    const float gi = sigmoid_fast(pi), gj = tanh_fast(pj), gf = sigmoid_fast(pf), go = sigmoid_fast(po);
+    const float c = a.c_prev[s0] * gf + gi * gj;
+    a.c[s0] = c;
+    a.h[s0] = f2bf(tanh_fast(c) * go);
+    a.gates[g0] = f2bf(gi);
+    a.gates[g0 + H] = f2bf(gj);
+    a.gates[g0 + 2 * H] = f2bf(gf);
+    a.gates[g0 + 3 * H] = f2bf(go);
+  }
+}
+
+struct BwdArgs {
+  const bf16_t* dg_next;  // dG[t + 1] [B, 4H], null: no prologue GEMM (t = T - 1)
+  const bf16_t* wh;       // kernel[I:] [H, 4H]
+  const bf16_t* gates;    // gates[t] [B, 4H], null: GEMM only (the dh0 launch)
+  const float* c;         // cs[t]
+  const float* c_prev;    // cs[t - 1] or c0
+  const bf16_t* dh_out;   // dhs[t] [B, H]
+  const bf16_t* dh_last;  // the final state's dh, added at t = T - 1 (else null)
+  float* dc_carry;        // [B, H] fp32, in place: in dL/dc_t from later steps, out dL/dc_{t-1}
+  bf16_t* dg;             // dG[t] [B, 4H]
+  bf16_t* dh0;            // the GEMM-only launch's output [B, H]
+  int B, H;
+};
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void lstm_step_bwd(BwdArgs a) {
+  constexpr int NT = U / 16;
+  __shared__ float red[kWaves * NT * 4 * kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+
+  float dhr[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) dhr[nt] = 0.f;
+  if (a.dg_next != nullptr) {                      // block-uniform
+    float4v acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+    const int arow = row0 + lr;
+    const bool a_ok = arow < a.B;
+    const bf16_t* a_lane = a.dg_next + static_cast<int64_t>(a_ok ? arow : 0) * 4 * H + lk;
+    const bf16_t* b_lane = a.wh + static_cast<int64_t>(slice * U + lr) * 4 * H + lk;
+    skinny_gemm<NT>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * 4 * H, 4 * H / kStep, wave, acc);
+    reduce_waves<NT>(red, acc, wave, lane, dhr);
+  }
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 4 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    if (a.gates == nullptr) {
+      a.dh0[s0] = f2bf(dhr[nt]);
+      continue;
+    }
+    float dh = dhr[nt] + bf2f(a.dh_out[s0]);
+    if (a.dh_last != nullptr) dh += bf2f(a.dh_last[s0]);
+    const float gi = bf2f(a.gates[g0]), gj = bf2f(a.gates[g0 + H]);
+    const float gf = bf2f(a.gates[g0 + 2 * H]), go = bf2f(a.gates[g0 + 3 * H]);
+    const float tc = tanh_fast(a.c[s0]);
+    const float dc = a.dc_carry[s0] + dh * go * (1.0f - tc * tc);
+    a.dg[g0] = f2bf(dc * gj * gi * (1.0f - gi));
+    a.dg[g0 + H] = f2bf(dc * gi * (1.0f - gj * gj));
+    a.dg[g0 + 2 * H] = f2bf(dc * a.c_prev[s0] * gf * (1.0f - gf));
+    a.dg[g0 + 3 * H] = f2bf(dh * tc * go * (1.0f - go));
+    a.dc_carry[s0] = dc * gf;
+  }
+}
+
+constexpr int kBf16 = 0;       // the dtype code of the entry points (1: fp32, refused)
+
+// hidden units per block: 32 where that still gives every CU of the device a block, else 16
+int pick_u(int B, int H) {
+  const int64_t tiles = ceil_div(B, kRows);
+  return tiles * (H / 32) >= 256 ? 32 : 16;
+}
+
+bool supported(int T, int B, int H, int dtype) {
+  return dtype == kBf16 && T >= 1 && B >= 1 && H >= 32 && H % 32 == 0 && static_cast<int64_t>(B) * 4 * H < (1LL << 31) &&
+         ceil_div(B, kRows) <= 65535;
+}
+
+}  // namespace
+
+// Units per block the step kernels use for this problem (16 or 32); 0 where the entry points refuse it.
+MDTF_EXPORT int mdtf_lstm_units(int T, int B, int H, int dtype) { return supported(T, B, H, dtype) ? pick_u(B, H) : 0; }
+
+// The recurrence over t = 0 .. T - 1: one pack launch and T step launches on `st`.  xg [T, B, 4H] bf16 (input half,
+// bias included), wh = kernel[I:] [H, 4H] bf16, wt: workspace of 4 * H * H bf16, h0 [B, H] bf16, c0 [B, H] fp32;
+// out: hs [T, B, H] bf16, cs [T, B, H] fp32, gates [T, B, 4H] bf16.  Every pointer 16-byte aligned.
+MDTF_EXPORT int mdtf_lstm_fwd(const void* xg, const void* wh, void* wt, const void* h0, const float* c0, void* hs,
+                              float* cs, void* gates, int T, int B, int H, float forget_bias, int dtype,
+                              hipStream_t st) {
+  if (!supported(T, B, H, dtype)) return MDTF_EUNSUPPORTED;
+  if (!xg || !wh || !wt || !h0 || !c0 || !hs || !cs || !gates) return MDTF_EINVAL;
+  const int U = pick_u(B, H);
+  lstm_pack_w<<<dim3(4 * H / 32, H / 32), 256, 0, st>>>(static_cast<const bf16_t*>(wh), static_cast<bf16_t*>(wt), H, U);
+  MDTF_LAUNCH_CHECK();
+  const int64_t sh = static_cast<int64_t>(B) * H;
+  const dim3 grid(H / U, static_cast<unsigned>(ceil_div(B, kRows)));
+  for (int t = 0; t < T; ++t) {
+    FwdArgs a;
+    a.xg = static_cast<const bf16_t*>(xg) + t * 4 * sh;
+    a.wt = static_cast<const bf16_t*>(wt);
+    a.h_prev = t ? static_cast<const bf16_t*>(hs) + (t - 1) * sh : static_cast<const bf16_t*>(h0);
+    a.c_prev = t ? cs + (t - 1) * sh : c0;
+    a.h = static_cast<bf16_t*>(hs) + t * sh;
+    a.c = cs + t * sh;
+    a.gates = static_cast<bf16_t*>(gates) + t * 4 * sh;
+    a.B = B;
+    a.H = H;
+    a.forget_bias = forget_bias;
+    if (U == 32)
+      lstm_step_fwd<32><<<grid, kWaves * kWave, 0, st>>>(a);
+    else
+      lstm_step_fwd<16><<<grid, kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+  }
+  return MDTF_OK;
+}
+
+// The recurrence backwards, t = T - 1 .. 0, then the GEMM-only launch for dh0: T + 1 launches on `st`.
+// wh = kernel[I:] [H, 4H] bf16; gates, cs, c0 as the forward left them; dhs [T, B, H] bf16; dh_last [B, H] bf16 or
+// null; dc_carry [B, H] fp32 holds dL/dc_T on entry and dL/dc_0 on return; out: dg [T, B, 4H] bf16, dh0 [B, H] bf16.
+MDTF_EXPORT int mdtf_lstm_bwd(const void* wh, const void* gates, const float* cs, const float* c0, const void* dhs,
+                              const void* dh_last, float* dc_carry, void* dg, void* dh0, int T, int B, int H,
+                              int dtype, hipStream_t st) {
+  if (!supported(T, B, H, dtype)) return MDTF_EUNSUPPORTED;
+  if (!wh || !gates || !cs || !c0 || !dhs || !dc_carry || !dg || !dh0) return MDTF_EINVAL;
+  const int U = pick_u(B, H);
+  const int64_t sh = static_cast<int64_t>(B) * H;
+  const dim3 grid(H / U, static_cast<unsigned>(ceil_div(B, kRows)));
+  for (int t = T - 1; t >= -1; --t) {
+    BwdArgs a;
+    a.dg_next = t < T - 1 ? static_cast<const bf16_t*>(dg) + (t + 1) * 4 * sh : nullptr;
+    a.wh = static_cast<const bf16_t*>(wh);
+    a.gates = t >= 0 ? static_cast<const bf16_t*>(gates) + t * 4 * sh : nullptr;
+    a.c = t >= 0 ? cs + t * sh : nullptr;
+    a.c_prev = t > 0 ? cs + (t - 1) * sh : c0;
+    a.dh_out = t >= 0 ? static_cast<const bf16_t*>(dhs) + t * sh : nullptr;
+    a.dh_last = t == T - 1 ? static_cast<const bf16_t*>(dh_last) : nullptr;
+    a.dc_carry = dc_carry;
+    a.dg = t >= 0 ? static_cast<bf16_t*>(dg) + t * 4 * sh : nullptr;
+    a.dh0 = static_cast<bf16_t*>(dh0);
+    a.B = B;
+    a.H = H;
+    if (U == 32)
+      lstm_step_bwd<32><<<grid, kWaves * kWave, 0, st>>>(a);
+    else
+      lstm_step_bwd<16><<<grid, kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+  }
+  return MDTF_OK;
+}

@@ -274,6 +274,13 @@ def dense(layer_name, x, out_features, act=None, initializer=None):
         return y.reshape(*shp[:-1], out_features)
 
 
+def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_state=None):
+    """One LSTM layer over ``x`` [B, T, I] (``time_major``: [T, B, I]): ``(outputs, LSTMStateTuple(c, h))`` with the
+    variables ``<layer_name>/lstm_cell/kernel`` and ``.../bias``.  Stack layers by calling it again on the outputs."""
+    cell = ops.rnn_cell.LSTMCell(num_units, forget_bias=forget_bias)
+    return ops.dynamic_rnn(cell, x, initial_state=initial_state, time_major=time_major, scope=layer_name)
+
+
 def layer_norm(layer_name, x, epsilon=1e-12):
     with V.variable_scope(layer_name):
         g = V.get_variable('gamma', [x.shape[-1]], initializer=V.constant_initializer(1.0), keep_fp32=True)

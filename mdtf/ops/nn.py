@@ -487,3 +487,10 @@ def add_n(ts):
     for t in ts[1:]:
         out = out + t
     return out
+
+
+# ---------------------------------------------------------------------------
+# recurrent (tf.nn.rnn_cell, tf.nn.dynamic_rnn)
+# ---------------------------------------------------------------------------
+from . import rnn_cell  # noqa: E402
+from .rnn_cell import dynamic_rnn  # noqa: E402,F401

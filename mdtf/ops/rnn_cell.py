@@ -1,0 +1,78 @@
+"""``tf.nn.rnn_cell`` and ``tf.nn.dynamic_rnn`` for the LSTM of ``ops/rnn.py`` (``mdtf.nn.rnn_cell``,
+``mdtf.nn.dynamic_rnn``).
+
+A cell owns no tensors: ``dynamic_rnn`` creates ``<scope or "rnn">/lstm_cell/kernel`` [I + H, 4H] and ``.../bias``
+[4H] on first use -- TF's names and layout (gate order i, j, f, o; the input rows first), so a ``Saver`` bundle matches
+-- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`.  Peepholes, projection and cell clipping are not
+implemented; nor are GRU / vanilla cells, ``MultiRNNCell`` (stack layers by calling ``dynamic_rnn`` under different
+scopes), dropout and bidirectional wrappers.
+"""
+import collections
+
+import torch
+
+LSTMStateTuple = collections.namedtuple("LSTMStateTuple", ("c", "h"))
+
+
+class LSTMCell(object):
+    """``tf.nn.rnn_cell.LSTMCell(num_units, forget_bias=1.0)``; ``initializer`` fills the kernel (default: Xavier
+    uniform, as TF's), the bias starts at zero."""
+
+    def __init__(self, num_units, forget_bias=1.0, name=None, use_peepholes=False, cell_clip=None, initializer=None,
+                 num_proj=None, state_is_tuple=True):
+        for what, on in (("use_peepholes", use_peepholes), ("cell_clip", cell_clip is not None),
+                         ("num_proj", num_proj is not None), ("state_is_tuple=False", not state_is_tuple)):
+            if on:
+                raise NotImplementedError("LSTMCell: %s is not implemented" % what)
+        self.num_units = int(num_units)
+        self.forget_bias = float(forget_bias)
+        self.initializer = initializer
+        self.name = name or "lstm_cell"
+
+    @property
+    def state_size(self):
+        return LSTMStateTuple(self.num_units, self.num_units)
+
+    @property
+    def output_size(self):
+        return self.num_units
+
+    def zero_state(self, batch_size, dtype=torch.float32, device=None):
+        from ..train import variables as V
+        device = device if device is not None else V.get_store().device
+        z = torch.zeros((batch_size, self.num_units), dtype=dtype, device=device)
+        return LSTMStateTuple(z, z.clone())
+
+    def variables(self, input_size):
+        """The reads of ``<scope>/<name>/kernel`` and ``.../bias`` (created on first use)."""
+        from ..train import variables as V
+        h = self.num_units
+        with V.variable_scope(self.name):
+            kernel = V.get_variable("kernel", [input_size + h, 4 * h],
+                                    initializer=self.initializer or V.xavier_initializer())
+            bias = V.get_variable("bias", [4 * h], initializer=V.constant_initializer(0.0))
+        return kernel, bias
+
+
+BasicLSTMCell = LSTMCell      # the same cell; its variables are named ``lstm_cell`` too unless ``name`` says otherwise
+
+
+def dynamic_rnn(cell, inputs, sequence_length=None, initial_state=None, dtype=None, time_major=False, scope=None):
+    """``tf.nn.dynamic_rnn``: ``(outputs, LSTMStateTuple(c, h))`` for ``inputs`` [B, T, I] (``time_major``: [T, B, I]).
+    Without ``initial_state`` the state starts at zero (in ``dtype`` or the dtype of ``inputs``).  On the HIP path
+    the returned ``c`` is fp32."""
+    from . import rnn
+    from ..train import variables as V
+    if not isinstance(cell, LSTMCell):
+        raise TypeError("dynamic_rnn: only LSTMCell / BasicLSTMCell cells are implemented, got %r" % (cell,))
+    if inputs.dim() != 3:
+        raise ValueError("dynamic_rnn: inputs must be rank 3, got %s" % (tuple(inputs.shape),))
+    x = inputs if time_major else inputs.transpose(0, 1).contiguous()    # the kernels are time-major
+    batch = x.shape[1]
+    if initial_state is None:
+        initial_state = cell.zero_state(batch, dtype or x.dtype, device=x.device)
+    c0, h0 = initial_state
+    with V.variable_scope(scope if scope is not None else "rnn"):
+        kernel, bias = cell.variables(x.shape[2])
+    hs, h_t, c_t = rnn.lstm(x, kernel, bias, h0, c0, cell.forget_bias, sequence_length)
+    return (hs if time_major else hs.transpose(0, 1)), LSTMStateTuple(c_t, h_t)
