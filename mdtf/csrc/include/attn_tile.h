@@ -127,4 +127,25 @@ __global__ void __launch_bounds__(256) attn_bwd_pre(const bf16_t* __restrict__ o
   }
 }
 
+// ---- encoder-decoder attention (attention_cross.hip): Sq queries against Sk keys of another sequence
+// keep bit of element (bh, q, k) of a [B*nh, Sq, Sk] probability tensor; with Sq == Sk the stream of keep_elem
+__device__ __forceinline__ bool keep_elem_x(uint32_t seed, int bh, int Sq, int Sk, int q, int k, uint32_t thr) {
+  const uint32_t idx = ((uint32_t)bh * Sq + (uint32_t)q) * Sk + (uint32_t)k;
+  return hash_u32(idx * 0x9E3779B1u ^ seed) >= thr;
+}
+
+// number of visible keys of batch item b: kv_len[b] clamped to [0, Sk], Sk without a length buffer.  b is
+// block-uniform, so this is one scalar load per block.
+__device__ __forceinline__ int kv_length(const int* kv_len, int b, int Sk) {
+  return kv_len ? min(max(__builtin_amdgcn_readfirstlane(kv_len[b]), 0), Sk) : Sk;
+}
+
+// zero `rows` rows x D bf16 columns at p (row stride ld elements) with 16-B stores, all NT threads of the block
+template <int D>
+__device__ __forceinline__ void zero_rows(bf16_t* p, int rows, int ld, int tid) {
+  constexpr int CH = D / 8;                      // 16-B chunks per row
+  for (int c = tid; c < rows * CH; c += NT)
+    *reinterpret_cast<uint4*>(p + (long long)(c / CH) * ld + (c % CH) * 8) = make_uint4(0u, 0u, 0u, 0u);
+}
+
 }  // namespace

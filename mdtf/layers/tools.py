@@ -281,6 +281,48 @@ def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_st
     return ops.dynamic_rnn(cell, x, initial_state=initial_state, time_major=time_major, scope=layer_name)
 
 
+def attention_layer(layer_name, from_tensor, to_tensor, num_heads, size_per_head, to_lengths=None,
+                    attention_mask=None, dropout=0.0, causal=False):
+    """BERT's ``attention_layer``: multi-head attention of ``from_tensor`` [B, F, W] over ``to_tensor`` [B, T, W'],
+    returning the context [B, F, num_heads * size_per_head] (no output projection).  Variables ``query/kernel``,
+    ``query/bias``, ``key/...``, ``value/...`` under ``layer_name``.
+
+    ``to_tensor is from_tensor`` without ``to_lengths``: self-attention, one fused q | k | v projection and
+    ``fused_attention`` (``causal`` passed through).  Otherwise encoder-decoder attention: a query projection, one
+    fused key | value projection and ``cross_attention``, item b restricted to its first ``to_lengths[b]`` positions
+    of ``to_tensor``; ``causal`` has no meaning between two sequences and raises.
+    ``attention_mask``: additive [B, T] key mask or None.  ``dropout`` applies while training only."""
+    from ..ops import transformer as T
+    from ..train import step as S
+    self_attention = to_tensor is from_tensor and to_lengths is None
+    if causal and not self_attention:
+        raise ValueError("attention_layer: causal=True needs to_tensor is from_tensor and no to_lengths")
+    B, F_ = from_tensor.shape[0], from_tensor.shape[1]
+    T_ = to_tensor.shape[1]
+    H = num_heads * size_per_head
+    ws, bs = {}, {}
+    with V.variable_scope(layer_name):
+        # created value, key, query: the flat parameter space lays variables out in reverse creation order, so the
+        # biases of a fused projection end up adjacent in q | k | v order (models/bert.py)
+        for nm, src in (("value", to_tensor), ("key", to_tensor), ("query", from_tensor)):
+            with V.variable_scope(nm):
+                ws[nm] = V.get_variable('kernel', [src.shape[-1], H],
+                                        initializer=V.truncated_normal_initializer(stddev=0.02))
+                bs[nm] = V.get_variable('bias', [H], initializer=V.constant_initializer(0.0))
+    drop = dropout if S.is_training() else 0.0
+    x = from_tensor.reshape(B * F_, from_tensor.shape[-1])
+    if self_attention:
+        order = ("query", "key", "value")
+        qkv = ops.dense_multi(x, [ws[n] for n in order], [bs[n] for n in order]).reshape(B * F_, 3 * H)
+        ctx = T.fused_attention(qkv, B, F_, num_heads, attention_mask, drop, causal=causal)
+    else:
+        q = ops.dense(x, ws["query"], bs["query"]).reshape(B * F_, H)
+        y = to_tensor.reshape(B * T_, to_tensor.shape[-1])
+        kv = ops.dense_multi(y, [ws["key"], ws["value"]], [bs["key"], bs["value"]]).reshape(B * T_, 2 * H)
+        ctx = T.cross_attention(q, kv, B, F_, T_, num_heads, attention_mask, to_lengths, drop)
+    return ctx.reshape(B, F_, H)
+
+
 def layer_norm(layer_name, x, epsilon=1e-12):
     with V.variable_scope(layer_name):
         g = V.get_variable('gamma', [x.shape[-1]], initializer=V.constant_initializer(1.0), keep_fp32=True)

@@ -450,3 +450,120 @@ def fused_attention(qkv, batch, seq, heads, mask=None, dropout=0.0, causal=False
     q, k, v = qkv.reshape(batch, seq, 3, heads, dh).unbind(2)
     ctx = attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), mask, dropout)
     return ctx.transpose(1, 2).reshape(batch * seq, H)
+
+
+N.register("mdtf_attn_fwd_cross", [N.P] * 6 + [N.I] * 5 + [N.F, N.F, N.U, N.P, N.P])
+N.register("mdtf_attn_bwd_cross", [N.P] * 10 + [N.I] * 5 + [N.F, N.F, N.U, N.P, N.P])
+_EUNSUPPORTED = -2      # MdtfStatus (include/mdtf_common.h)
+
+
+class _CrossUnsupported(Exception):
+    """The cross-attention entry point refused the shape (32-bit offsets): the caller takes the PyTorch expression."""
+
+
+class _CrossAttention(torch.autograd.Function):
+    """softmax(Q K^T / sqrt(d) + mask) V with queries from ``q`` [B*Sq, H], keys / values from ``kv`` [B*Sk, 2H] and
+    item b restricted to its first ``lengths[b]`` keys (``csrc/attention_cross.hip``: Sq, Sk % 64 == 0, head dim
+    64 / 128).  ``lengths``: int32 on the device or None; the kernels read it, the host never does."""
+
+    @staticmethod
+    def forward(ctx, q, kv, mask, lengths, B, Sq, Sk, nh, p_drop, seed):
+        q, kv = q.contiguous(), kv.contiguous()
+        H = q.shape[-1]
+        dh = H // nh
+        out = torch.empty((B * Sq, H), dtype=q.dtype, device=q.device)
+        lse = torch.empty((B * nh, Sq), dtype=torch.float32, device=q.device)
+        m = mask.float().contiguous() if mask is not None else None
+        scale = 1.0 / math.sqrt(dh)
+        rc = N.fn("mdtf_attn_fwd_cross")(N.ptr(q), N.ptr(kv), N.ptr(m), N.ptr(lengths), N.ptr(out), N.ptr(lse), B, Sq,
+                                         Sk, nh, dh, scale, float(p_drop), seed, N.ptr(_seed_off(p_drop, q.device)),
+                                         N.stream_ptr())
+        if rc == _EUNSUPPORTED:
+            raise _CrossUnsupported()
+        N.check(rc, "attn_fwd_cross")
+        ctx.save_for_backward(q, kv, out, lse, m, lengths)
+        ctx.args = (B, Sq, Sk, nh, float(p_drop), seed, scale, dh)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv, out, lse, m, lengths = ctx.saved_tensors
+        B, Sq, Sk, nh, p_drop, seed, scale, dh = ctx.args
+        dout = dout.contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        ws = torch.empty((B * nh * Sq,), dtype=torch.float32, device=q.device)
+        N.check(N.fn("mdtf_attn_bwd_cross")(N.ptr(q), N.ptr(kv), N.ptr(m), N.ptr(lengths), N.ptr(out), N.ptr(dout),
+                                            N.ptr(lse), N.ptr(dq), N.ptr(dkv), N.ptr(ws), B, Sq, Sk, nh, dh, scale,
+                                            p_drop, seed, N.ptr(_seed_off(p_drop, q.device)), N.stream_ptr()),
+                "attn_bwd_cross")
+        return dq, dkv, None, None, None, None, None, None, None, None
+
+
+def _cross_attention_torch(q, kv, B, Sq, Sk, nh, mask, lengths, dropout):
+    """The fp32 PyTorch expression of :func:`cross_attention`: -inf on the columns >= length, zeros (not NaN) for the
+    rows of an item of length 0."""
+    H = q.shape[-1]
+    dh = H // nh
+    qh = q.reshape(B, Sq, nh, dh).transpose(1, 2).float()
+    k, v = (t.transpose(1, 2).float() for t in kv.reshape(B, Sk, 2, nh, dh).unbind(2))
+    s = torch.matmul(qh, k.transpose(-1, -2)) / math.sqrt(dh)
+    if mask is not None:
+        s = s + mask.float()[:, None, None, :]
+    empty = None
+    if lengths is not None:
+        n = lengths.to(q.device).long().clamp(0, Sk)
+        empty = (n == 0)[:, None]
+        # an empty item keeps finite scores (a softmax over -inf alone is NaN, and so is its gradient); its
+        # probabilities are zeroed below
+        hidden = (torch.arange(Sk, device=q.device)[None, :] >= n[:, None]) & ~empty
+        s = s.masked_fill(hidden[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, -1)
+    if empty is not None:
+        p = p * (~empty)[:, :, None, None].to(p.dtype)
+    if dropout:
+        p = F.dropout(p, dropout, True)
+    return torch.matmul(p, v).transpose(1, 2).reshape(B * Sq, H).to(q.dtype)
+
+
+def cross_attention(q, kv, batch, q_len, kv_len, heads, mask=None, kv_lengths=None, dropout=0.0):
+    """Encoder-decoder attention: queries ``q`` [B*Sq, H] of one sequence over the keys / values ``kv`` [B*Sk, 2H]
+    (k | v, heads contiguous inside each half: one ``dense_multi`` over the other sequence) to the context [B*Sq, H].
+
+    ``mask``: additive [B, Sk] key mask or None.  ``kv_lengths``: item b sees keys ``k < kv_lengths[b]`` only (values
+    clamped to [0, Sk]; an item of length 0 gives zeros); a device int32 tensor is handed to the kernels as it is
+    (they read it on the device, so it can be updated in place inside a captured step), a CPU tensor or a list is
+    copied to the device once; None = every key.
+    GPU, bf16, Sq and Sk % 64 == 0, head dim 64 / 128: the length-aware tiled kernels
+    (``csrc/attention_cross.hip``: key tiles past an item's length are neither loaded nor computed); otherwise an
+    fp32 PyTorch expression.
+    """
+    H = q.shape[-1]
+    if heads <= 0 or H % heads:
+        raise ValueError("cross_attention: %d heads do not divide the width %d" % (heads, H))
+    if q.dim() != 2 or q.shape[0] != batch * q_len:
+        raise ValueError("cross_attention: q %s is not [batch * q_len = %d, H]" % (tuple(q.shape), batch * q_len))
+    if kv.dim() != 2 or tuple(kv.shape) != (batch * kv_len, 2 * H):
+        raise ValueError("cross_attention: kv %s is not [batch * kv_len = %d, 2H = %d]"
+                         % (tuple(kv.shape), batch * kv_len, 2 * H))
+    if mask is not None and tuple(mask.shape) != (batch, kv_len):
+        raise ValueError("cross_attention: mask %s is not [batch, kv_len]" % (tuple(mask.shape),))
+    if kv_lengths is not None:
+        if not torch.is_tensor(kv_lengths):
+            kv_lengths = torch.as_tensor(kv_lengths, dtype=torch.int32)
+        if tuple(kv_lengths.shape) != (batch,):
+            raise ValueError("cross_attention: kv_lengths %s is not [batch = %d]" % (tuple(kv_lengths.shape), batch))
+        if kv_lengths.is_floating_point():
+            raise ValueError("cross_attention: kv_lengths must be integers")
+    dh = H // heads
+    if N.use_native(q) and q.dtype == torch.bfloat16 and kv.dtype == q.dtype and flash_ok(q_len, dh) and \
+            flash_ok(kv_len, dh):
+        lengths = kv_lengths
+        if lengths is not None and not (lengths.device == q.device and lengths.dtype == torch.int32
+                                        and lengths.is_contiguous()):
+            lengths = lengths.to(q.device, torch.int32).contiguous()
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout else 0
+        try:
+            return _CrossAttention.apply(q, kv, mask, lengths, batch, q_len, kv_len, heads, float(dropout), seed)
+        except _CrossUnsupported:
+            pass
+    return _cross_attention_torch(q, kv, batch, q_len, kv_len, heads, mask, kv_lengths, dropout)
