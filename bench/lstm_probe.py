@@ -14,6 +14,10 @@ first) and the replay is timed with device events ``--reps`` times (median, min,
 ``--rounds`` times.  ``step_us`` is the native forward per time step, to hold against the dependent-launch floor.
 ``loses`` is set where the native median is above ``nn.LSTM``'s by more than that one's own min .. max spread.  One
 JSON line per shape and pass.  Needs a GPU.
+
+``--lengths {full,uniform,sorted}`` and ``--bidirectional`` time the recurrences alone instead (no input GEMM, no
+weight gradients), per step, at the same shapes: what the length test costs a full-length batch, what skipping dead
+tiles saves a ragged one, and one fused two-direction call against two calls (``recurrence_passes``).
 """
 import argparse
 import json
@@ -72,11 +76,82 @@ def library_passes(t, b, h, gen):
     return {"fwd": fwd, "fwd+bwd": both}
 
 
+def probe_lengths(kind, t, b, gen):
+    """``full``: every row T; ``uniform``: uniform in 1 .. T, in batch order; ``sorted``: the same, longest first (a
+    bucketed batch: the rows of a 16-row tile die together)."""
+    if kind == "full":
+        return torch.full((b,), t, dtype=torch.int32)
+    lens = torch.randint(1, t + 1, (b,), generator=gen, dtype=torch.int32)
+    return lens.sort(descending=True)[0] if kind == "sorted" else lens
+
+
+def recurrence_passes(t, b, h, gen, lens, bidirectional):
+    """The recurrences alone through the entry points, on buffers made once: name -> (forward, backward).  ``plain``:
+    ``mdtf_lstm_fwd`` / ``mdtf_lstm_bwd`` (no lengths, the kernels of the full-length path before lengths existed);
+    ``seq-full`` / ``seq-<kind>``: the length-aware kernels without and with ``lens``; ``bidirectional``: ``fused``
+    (both directions in every launch) and ``two-calls`` (a forward then a reverse call), both with ``lens``."""
+    from mdtf.ops import _native as N, rnn
+    dev, st = "cuda", N.stream_ptr
+    new = lambda *shape, dtype=torch.bfloat16: torch.randn(shape, generator=gen).to(dev).to(dtype)
+
+    def direction():
+        d = dict(xg=new(t, b, 4 * h), wh=new(h, 4 * h) * (2 * h) ** -0.5, wt=new(4 * h * h), h0=new(b, h) * 0.5,
+                 c0=new(b, h, dtype=torch.float32) * 0.5, hs=new(t, b, h), cs=new(t, b, h, dtype=torch.float32),
+                 gates=new(t, b, 4 * h), h_fin=new(b, h), c_fin=new(b, h, dtype=torch.float32), dhs=new(t, b, h),
+                 dh_t=new(b, h), carry=new(b, h, dtype=torch.float32), dg=new(t, b, 4 * h), dh0=new(b, h))
+        d["wh"] = d["wh"].contiguous()
+        d["fwd"] = tuple(d[k] for k in ("xg", "wh", "wt", "h0", "c0", "hs", "cs", "gates", "h_fin", "c_fin"))
+        d["bwd"] = tuple(d[k] for k in ("wh", "gates", "cs", "c0", "dhs", "dh_t", "carry", "dg", "dh0"))
+        return d
+    a, z = direction(), direction()
+    lens = lens.to(dev)
+
+    def seq(dirs, reverse, lengths):
+        ft, bt = rnn._table([d["fwd"] for d in dirs]), rnn._table([d["bwd"] for d in dirs])
+        return (lambda: N.check(N.fn("mdtf_lstm_fwd_seq")(ft, len(dirs), reverse, N.ptr(lengths), t, b, h, 4 * h, 1.0,
+                                                          rnn.BF16, st()), "lstm_fwd_seq"),
+                lambda: N.check(N.fn("mdtf_lstm_bwd_seq")(bt, len(dirs), reverse, N.ptr(lengths), t, b, h, rnn.BF16,
+                                                          st()), "lstm_bwd_seq"))
+    if bidirectional:
+        (f_a, b_a), (f_z, b_z) = seq([a], 0, lens), seq([z], 1, lens)
+        return {"fused": seq([a, z], 0b10, lens), "two-calls": (lambda: (f_a(), f_z()), lambda: (b_a(), b_z()))}
+    P = N.ptr
+    plain = (lambda: N.check(N.fn("mdtf_lstm_fwd")(*[P(x) for x in a["fwd"][:8]], t, b, h, 1.0, rnn.BF16, st()), "lstm_fwd"),
+             lambda: N.check(N.fn("mdtf_lstm_bwd")(*[P(x) for x in a["bwd"]], t, b, h, rnn.BF16, st()), "lstm_bwd"))
+    return {"plain": plain, "seq-full": seq([a], 0, None), "seq-lengths": seq([a], 0, lens)}
+
+
+def recurrence_probe(args, gen):
+    """One JSON line per shape and pass: us per step of every variant of :func:`recurrence_passes`, median (min, max)
+    over the replays, the variants alternating ``--rounds`` times.  A backward "step" is one of its T + 1 launches."""
+    for t, b, h in SHAPES:
+        lens = probe_lengths(args.lengths or "full", t, b, gen)
+        variants = recurrence_passes(t, b, h, gen, lens, args.bidirectional)
+        for i, which in enumerate(("fwd", "bwd")):
+            rec = {"probe": "lstm_recurrence", "T": t, "B": b, "H": h, "pass": which, "lengths": args.lengths or "full",
+                   "mean_length": round(float(lens.float().mean()), 1), "iters": args.iters, "reps": args.reps,
+                   "rounds": args.rounds}
+            times = {k: [] for k in variants}
+            for _ in range(args.rounds):
+                for key, fs in variants.items():
+                    times[key].append(graph_time(fs[i], args.iters, args.reps))
+            for key, ts in times.items():
+                steps = t + i
+                rec[key] = {"step_us": round(sorted(x[0] for x in ts)[len(ts) // 2] / steps, 2),
+                            "step_us_min": round(min(x[1] for x in ts) / steps, 2),
+                            "step_us_max": round(max(x[2] for x in ts) / steps, 2)}
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=3, help="sequences per captured graph")
     p.add_argument("--reps", type=int, default=7, help="timed replays per measurement")
     p.add_argument("--rounds", type=int, default=3, help="alternations of the variants")
+    p.add_argument("--lengths", choices=["full", "uniform", "sorted"], default=None,
+                   help="time the recurrences alone with these per-row lengths (see recurrence_passes)")
+    p.add_argument("--bidirectional", action="store_true",
+                   help="time one fused two-direction call against two one-direction calls")
     args = p.parse_args()
     sys.argv = sys.argv[:1]                        # mdtf's own flags parse the command line on first use
     if not torch.cuda.is_available():
@@ -85,6 +160,8 @@ def main():
     from mdtf.ops import _native, rnn
     _native.lib()
     gen = torch.Generator().manual_seed(0)
+    if args.lengths or args.bidirectional:
+        return recurrence_probe(args, gen)
     for t, b, h in SHAPES:
         ours, lib = mdtf_passes(t, b, h, gen), library_passes(t, b, h, gen)
         for which in ("fwd", "fwd+bwd"):

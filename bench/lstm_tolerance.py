@@ -1,4 +1,5 @@
-"""Measure the bf16 limits of ``tests/lstm_helpers.py`` on the CPU (no GPU, no kernel involved).
+"""Measure the bf16 limits of ``tests/lstm_helpers.py`` and ``tests/test_lstm_lengths.py`` on the CPU (no GPU, no
+kernel involved).
 
 The LSTM of ``mdtf/ops/rnn.py`` as an fp32 PyTorch expression, forward and backward, rounded to bf16 at exactly the
 points where the HIP path rounds: xg (the input half with its bias), h_t, the stored post-activation gates, dG, and the
@@ -7,6 +8,12 @@ error against the fp64 oracle, ``max |got - ref| / max |ref|`` per tensor, worst
 ``MEASURED_BF16``; the tests allow the kernels twice that.
 
     python -m bench.lstm_tolerance
+
+``--lengths``: the same expression with per-row lengths, in both directions and for the two directions at once (whose
+dx is one bf16 tensor the second direction adds into), over the cases of ``tests/test_lstm_lengths.py`` against its
+oracles: ``MEASURED_LENGTHS``.
+
+    python -m bench.lstm_tolerance --lengths
 """
 import os
 import sys
@@ -21,45 +28,75 @@ def _r(t):
     return t.bfloat16().float()
 
 
-def emulate(c):
+def emulate(c, reverse=False, dx_base=None):
+    """``c.lengths`` (None: full length): a dead row keeps its state and emits zeros; ``reverse``: t runs from T - 1
+    down.  ``dx_base``: the bf16 dx of another direction that this one's product adds into."""
     t_n, b_n, i_n, h_n = c.shape
     wx, wh = c.kernel[:i_n], c.kernel[i_n:]
     x2 = c.x.reshape(t_n * b_n, i_n)
     xg = _r(x2 @ wx + c.bias).reshape(t_n, b_n, 4 * h_n)
+    lens = torch.tensor(c.lengths if c.lengths is not None else [t_n] * b_n)[:, None]
+    order = list(range(t_n - 1, -1, -1) if reverse else range(t_n))
     h, cell = c.h0, c.c0
-    hs, cs, gates = [], [], []
-    for t in range(t_n):
+    hs, cs, gates, h_prev, c_prev = ([None] * t_n for _ in range(5))
+    for t in order:
+        live = lens > t
         gi, gj, gf, go = (xg[t] + h @ wh).split(h_n, 1)
         gi, gj, gf, go = torch.sigmoid(gi), torch.tanh(gj), torch.sigmoid(gf + LH.FORGET_BIAS), torch.sigmoid(go)
-        cell = cell * gf + gi * gj
-        h = _r(torch.tanh(cell) * go)
-        hs.append(h)
-        cs.append(cell)
-        gates.append([_r(g) for g in (gi, gj, gf, go)])
-    carry, dg = c.dc_t.clone(), [None] * t_n
-    for t in range(t_n - 1, -1, -1):
+        h_prev[t], c_prev[t] = h, cell
+        cs[t] = cell * gf + gi * gj
+        h_new = _r(torch.tanh(cs[t]) * go)
+        hs[t] = torch.where(live, h_new, torch.zeros_like(h_new))
+        h, cell = torch.where(live, h_new, h), torch.where(live, cs[t], cell)
+        gates[t] = [_r(g) for g in (gi, gj, gf, go)]
+    h_fin, c_fin = h, cell
+    carry, dh_next, dg = c.dc_t.clone(), c.dh_t, [None] * t_n      # dh_next: dL/dh of the state a row holds, in fp32
+    for t in reversed(order):
+        live = lens > t
         gi, gj, gf, go = gates[t]
-        dh = c.dhs[t] + (c.dh_t if t == t_n - 1 else dg[t + 1] @ wh.t())
+        dh = c.dhs[t] + dh_next
         tc = torch.tanh(cs[t])
         dc = carry + dh * go * (1 - tc * tc)
-        c_prev = cs[t - 1] if t else c.c0
-        dg[t] = _r(torch.cat([dc * gj * gi * (1 - gi), dc * gi * (1 - gj * gj), dc * c_prev * gf * (1 - gf),
+        dg[t] = _r(torch.cat([dc * gj * gi * (1 - gi), dc * gi * (1 - gj * gj), dc * c_prev[t] * gf * (1 - gf),
                               dh * tc * go * (1 - go)], 1))
-        carry = dc * gf
+        dg[t] = torch.where(live, dg[t], torch.zeros_like(dg[t]))
+        carry, dh_next = torch.where(live, dc * gf, carry), torch.where(live, dg[t] @ wh.t(), dh_next)
     dg2 = torch.stack(dg, 0).reshape(t_n * b_n, 4 * h_n)
-    h_prev = torch.stack([c.h0] + hs[:-1], 0).reshape(t_n * b_n, h_n)
-    return dict(zip(LH.NAMES, (torch.stack(hs, 0), hs[-1], cs[-1], _r(dg2 @ wx.t()).reshape(c.x.shape),
-                               torch.cat([x2.t() @ dg2, h_prev.t() @ dg2], 0), dg2.sum(0), _r(dg[0] @ wh.t()),
-                               carry)))
+    hp = torch.stack(h_prev, 0).reshape(t_n * b_n, h_n)
+    dx = dg2 @ wx.t() if dx_base is None else dx_base.reshape(t_n * b_n, i_n) + dg2 @ wx.t()
+    return dict(zip(LH.NAMES, (torch.stack(hs, 0), h_fin, c_fin, _r(dx).reshape(c.x.shape),
+                               torch.cat([x2.t() @ dg2, hp.t() @ dg2], 0), dg2.sum(0), _r(dh_next), carry)))
+
+
+def _show(what, worst, err):
+    print("%s %s" % (what, " ".join("%s=%.3e" % kv for kv in err.items())))
+    return {k: max(worst[k], err[k]) for k in worst}
+
+
+def lengths_table():
+    import test_lstm_lengths as TL
+    worst = dict.fromkeys(LH.NAMES, 0.0)
+    for name in TL.LENGTHS:
+        c = TL.case(name)
+        for direction in ("fw", "bw"):
+            got = emulate(c, direction == "bw")
+            worst = _show("case %s %s" % (name, direction), worst, LH.errors(got, TL.reference(name, direction)))
+        if name not in TL.PAIRS:
+            continue
+        alt, ref_fw, ref_bw = TL.other(c), TL.reference(name, "fw"), TL.reference(name, "bw", True)
+        fw = emulate(c)
+        bw = emulate(alt, True, dx_base=fw["dx"])
+        worst = _show("case %s bidirectional bw" % name, worst, LH.errors(bw, dict(ref_bw, dx=ref_fw["dx"] + ref_bw["dx"])))
+    print("MEASURED_LENGTHS = {%s}" % ", ".join('"%s": %.2e' % kv for kv in worst.items()))
 
 
 def main():
+    if "--lengths" in sys.argv[1:]:
+        return lengths_table()
     worst = dict.fromkeys(LH.NAMES, 0.0)
     for name in "abcde":
         c = LH.case(name)
-        err = LH.errors(emulate(c), c.ref)
-        print("case %s %s" % (name, " ".join("%s=%.3e" % kv for kv in err.items())))
-        worst = {k: max(worst[k], err[k]) for k in worst}
+        worst = _show("case %s" % name, worst, LH.errors(emulate(c), c.ref))
     print("MEASURED_BF16 = {%s}" % ", ".join('"%s": %.2e' % kv for kv in worst.items()))
 
 

@@ -274,11 +274,23 @@ def dense(layer_name, x, out_features, act=None, initializer=None):
         return y.reshape(*shp[:-1], out_features)
 
 
-def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_state=None):
+def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_state=None, sequence_length=None):
     """One LSTM layer over ``x`` [B, T, I] (``time_major``: [T, B, I]): ``(outputs, LSTMStateTuple(c, h))`` with the
-    variables ``<layer_name>/lstm_cell/kernel`` and ``.../bias``.  Stack layers by calling it again on the outputs."""
+    variables ``<layer_name>/lstm_cell/kernel`` and ``.../bias``.  Stack layers by calling it again on the outputs.
+    ``sequence_length`` [B]: past its length a row emits zeros and keeps its state."""
     cell = ops.rnn_cell.LSTMCell(num_units, forget_bias=forget_bias)
-    return ops.dynamic_rnn(cell, x, initial_state=initial_state, time_major=time_major, scope=layer_name)
+    return ops.dynamic_rnn(cell, x, sequence_length=sequence_length, initial_state=initial_state,
+                           time_major=time_major, scope=layer_name)
+
+
+def bilstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, sequence_length=None):
+    """One bidirectional LSTM layer over ``x``: ``(outputs, (state_fw, state_bw))``, the outputs of the two directions
+    concatenated to ``2 * num_units`` features, with the variables ``<layer_name>/fw/lstm_cell/{kernel,bias}`` and
+    ``<layer_name>/bw/...``."""
+    cells = [ops.rnn_cell.LSTMCell(num_units, forget_bias=forget_bias) for _ in range(2)]
+    outs, states = ops.bidirectional_dynamic_rnn(cells[0], cells[1], x, sequence_length=sequence_length,
+                                                 time_major=time_major, scope=layer_name)
+    return torch.cat(outs, -1), states
 
 
 def attention_layer(layer_name, from_tensor, to_tensor, num_heads, size_per_head, to_lengths=None,

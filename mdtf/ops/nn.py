@@ -490,7 +490,7 @@ def add_n(ts):
 
 
 # ---------------------------------------------------------------------------
-# recurrent (tf.nn.rnn_cell, tf.nn.dynamic_rnn)
+# recurrent (tf.nn.rnn_cell, tf.nn.dynamic_rnn, tf.nn.bidirectional_dynamic_rnn)
 # ---------------------------------------------------------------------------
 from . import rnn_cell  # noqa: E402
-from .rnn_cell import dynamic_rnn  # noqa: E402,F401
+from .rnn_cell import bidirectional_dynamic_rnn, dynamic_rnn  # noqa: E402,F401

@@ -1,11 +1,12 @@
-"""``tf.nn.rnn_cell`` and ``tf.nn.dynamic_rnn`` for the LSTM of ``ops/rnn.py`` (``mdtf.nn.rnn_cell``,
-``mdtf.nn.dynamic_rnn``).
+"""``tf.nn.rnn_cell``, ``tf.nn.dynamic_rnn`` and ``tf.nn.bidirectional_dynamic_rnn`` for the LSTM of ``ops/rnn.py``
+(``mdtf.nn.rnn_cell``, ``mdtf.nn.dynamic_rnn``, ``mdtf.nn.bidirectional_dynamic_rnn``).
 
 A cell owns no tensors: ``dynamic_rnn`` creates ``<scope or "rnn">/lstm_cell/kernel`` [I + H, 4H] and ``.../bias``
 [4H] on first use -- TF's names and layout (gate order i, j, f, o; the input rows first), so a ``Saver`` bundle matches
--- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`.  Peepholes, projection and cell clipping are not
-implemented; nor are GRU / vanilla cells, ``MultiRNNCell`` (stack layers by calling ``dynamic_rnn`` under different
-scopes), dropout and bidirectional wrappers.
+-- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`, ``sequence_length`` included;
+``bidirectional_dynamic_rnn`` does the same under ``<scope or "bidirectional_rnn">/fw`` and ``.../bw`` through
+:func:`mdtf.ops.rnn.bilstm`.  Peepholes, projection and cell clipping are not implemented; nor are GRU / vanilla
+cells, ``MultiRNNCell`` (stack layers by calling ``dynamic_rnn`` under different scopes) and dropout wrappers.
 """
 import collections
 
@@ -76,3 +77,30 @@ def dynamic_rnn(cell, inputs, sequence_length=None, initial_state=None, dtype=No
         kernel, bias = cell.variables(x.shape[2])
     hs, h_t, c_t = rnn.lstm(x, kernel, bias, h0, c0, cell.forget_bias, sequence_length)
     return (hs if time_major else hs.transpose(0, 1)), LSTMStateTuple(c_t, h_t)
+
+
+def bidirectional_dynamic_rnn(cell_fw, cell_bw, inputs, sequence_length=None, initial_state_fw=None,
+                              initial_state_bw=None, dtype=None, time_major=False, scope=None):
+    """``tf.nn.bidirectional_dynamic_rnn``: ``((out_fw, out_bw), (state_fw, state_bw))``.  ``cell_bw`` reads row b
+    from ``sequence_length[b] - 1`` down to 0 and ``out_bw`` is in the time order of ``inputs``; past its length a row
+    is zero in both.  Variables: ``<scope or "bidirectional_rnn">/fw/lstm_cell/{kernel,bias}`` and ``.../bw/...``."""
+    from . import rnn
+    from ..train import variables as V
+    for cell in (cell_fw, cell_bw):
+        if not isinstance(cell, LSTMCell):
+            raise TypeError("bidirectional_dynamic_rnn: only LSTMCell / BasicLSTMCell cells are implemented, got %r"
+                            % (cell,))
+    if inputs.dim() != 3:
+        raise ValueError("bidirectional_dynamic_rnn: inputs must be rank 3, got %s" % (tuple(inputs.shape),))
+    x = inputs if time_major else inputs.transpose(0, 1).contiguous()
+    params = []
+    with V.variable_scope(scope if scope is not None else "bidirectional_rnn"):
+        for name, cell, state in (("fw", cell_fw, initial_state_fw), ("bw", cell_bw, initial_state_bw)):
+            if state is None:
+                state = cell.zero_state(x.shape[1], dtype or x.dtype, device=x.device)
+            c0, h0 = state
+            with V.variable_scope(name):
+                params.append(cell.variables(x.shape[2]) + (h0, c0))
+    res = rnn.bilstm(x, params[0], params[1], (cell_fw.forget_bias, cell_bw.forget_bias), sequence_length)
+    outs = tuple(hs if time_major else hs.transpose(0, 1) for hs, _, _ in res)
+    return outs, tuple(LSTMStateTuple(c_t, h_t) for _, h_t, c_t in res)
