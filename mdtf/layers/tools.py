@@ -283,6 +283,15 @@ def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_st
                            time_major=time_major, scope=layer_name)
 
 
+def gru(layer_name, x, num_units, time_major=False, initial_state=None, sequence_length=None):
+    """One GRU layer over ``x`` [B, T, I] (``time_major``: [T, B, I]): ``(outputs, state [B, num_units])`` with the
+    variables ``<layer_name>/gru_cell/gates/{kernel,bias}`` and ``.../candidate/{kernel,bias}``.  Stack layers by
+    calling it again on the outputs.  ``sequence_length`` [B]: past its length a row emits zeros and keeps its state."""
+    cell = ops.rnn_cell.GRUCell(num_units)
+    return ops.dynamic_rnn(cell, x, sequence_length=sequence_length, initial_state=initial_state,
+                           time_major=time_major, scope=layer_name)
+
+
 def bilstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, sequence_length=None):
     """One bidirectional LSTM layer over ``x``: ``(outputs, (state_fw, state_bw))``, the outputs of the two directions
     concatenated to ``2 * num_units`` features, with the variables ``<layer_name>/fw/lstm_cell/{kernel,bias}`` and

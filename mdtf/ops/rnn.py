@@ -23,8 +23,8 @@ they may change between replays of a captured step.  The two halves of the kerne
 slot when there is one, and ``dx = dG @ kernel[:I]^T`` is the dense data gradient.
 
 Every other case runs :func:`lstm_loop`, the definition as a PyTorch loop with fp32 gate math: CPU tensors,
-``MDTF_KERNELS=torch`` (the comparator), fp32 activations and other ``H``.  Not here: GRU and vanilla cells, peepholes,
-projection, cell clipping and multi-cell wrappers.
+``MDTF_KERNELS=torch`` (the comparator), fp32 activations and other ``H``.  Not here: vanilla cells, peepholes,
+projection, cell clipping and multi-cell wrappers (the GRU is ``ops/gru.py``).
 """
 import ctypes
 

@@ -1,12 +1,14 @@
-"""``tf.nn.rnn_cell``, ``tf.nn.dynamic_rnn`` and ``tf.nn.bidirectional_dynamic_rnn`` for the LSTM of ``ops/rnn.py``
-(``mdtf.nn.rnn_cell``, ``mdtf.nn.dynamic_rnn``, ``mdtf.nn.bidirectional_dynamic_rnn``).
+"""``tf.nn.rnn_cell``, ``tf.nn.dynamic_rnn`` and ``tf.nn.bidirectional_dynamic_rnn`` for the LSTM of ``ops/rnn.py`` and
+the GRU of ``ops/gru.py`` (``mdtf.nn.rnn_cell``, ``mdtf.nn.dynamic_rnn``, ``mdtf.nn.bidirectional_dynamic_rnn``).
 
 A cell owns no tensors: ``dynamic_rnn`` creates ``<scope or "rnn">/lstm_cell/kernel`` [I + H, 4H] and ``.../bias``
 [4H] on first use -- TF's names and layout (gate order i, j, f, o; the input rows first), so a ``Saver`` bundle matches
--- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`, ``sequence_length`` included;
-``bidirectional_dynamic_rnn`` does the same under ``<scope or "bidirectional_rnn">/fw`` and ``.../bw`` through
-:func:`mdtf.ops.rnn.bilstm`.  Peepholes, projection and cell clipping are not implemented; nor are GRU / vanilla
-cells, ``MultiRNNCell`` (stack layers by calling ``dynamic_rnn`` under different scopes) and dropout wrappers.
+-- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`, ``sequence_length`` included; a ``GRUCell`` gets
+``.../gru_cell/gates/{kernel,bias}`` [I + H, 2H] / [2H] (r then u) and ``.../gru_cell/candidate/{kernel,bias}``
+[I + H, H] / [H] and runs through :func:`mdtf.ops.gru.gru`.  ``bidirectional_dynamic_rnn`` runs LSTM cells under
+``<scope or "bidirectional_rnn">/fw`` and ``.../bw`` through :func:`mdtf.ops.rnn.bilstm`.  Peepholes, projection and
+cell clipping are not implemented; nor are vanilla cells, bidirectional GRUs, ``MultiRNNCell`` (stack layers by
+calling ``dynamic_rnn`` under different scopes) and dropout wrappers.
 """
 import collections
 
@@ -58,20 +60,69 @@ class LSTMCell(object):
 BasicLSTMCell = LSTMCell      # the same cell; its variables are named ``lstm_cell`` too unless ``name`` says otherwise
 
 
+class GRUCell(object):
+    """``tf.nn.rnn_cell.GRUCell(num_units)``: the reset gate is applied before the candidate product.
+    ``kernel_initializer`` fills both kernels (default: Xavier uniform, as TF's); ``bias_initializer`` fills the
+    candidate bias (default 0) and, where given, the gates bias, which otherwise starts at 1.0 as TF's does."""
+
+    def __init__(self, num_units, activation=None, kernel_initializer=None, bias_initializer=None, name=None):
+        if activation is not None and activation not in (torch.tanh, "tanh"):
+            raise NotImplementedError("GRUCell: only the tanh activation is implemented")
+        self.num_units = int(num_units)
+        self.kernel_initializer = kernel_initializer
+        self.bias_initializer = bias_initializer
+        self.name = name or "gru_cell"
+
+    @property
+    def state_size(self):
+        return self.num_units
+
+    @property
+    def output_size(self):
+        return self.num_units
+
+    def zero_state(self, batch_size, dtype=torch.float32, device=None):
+        from ..train import variables as V
+        device = device if device is not None else V.get_store().device
+        return torch.zeros((batch_size, self.num_units), dtype=dtype, device=device)
+
+    def variables(self, input_size):
+        """The reads of ``<scope>/<name>/gates/{kernel,bias}`` and ``.../candidate/{kernel,bias}`` (created on first
+        use)."""
+        from ..train import variables as V
+        h = self.num_units
+        out = []
+        with V.variable_scope(self.name):
+            for part, cols, bias0 in (("gates", 2 * h, 1.0), ("candidate", h, 0.0)):
+                with V.variable_scope(part):
+                    out.append(V.get_variable("kernel", [input_size + h, cols],
+                                              initializer=self.kernel_initializer or V.xavier_initializer()))
+                    out.append(V.get_variable("bias", [cols], initializer=self.bias_initializer
+                                              or V.constant_initializer(bias0)))
+        return tuple(out)
+
+
+
 def dynamic_rnn(cell, inputs, sequence_length=None, initial_state=None, dtype=None, time_major=False, scope=None):
-    """``tf.nn.dynamic_rnn``: ``(outputs, LSTMStateTuple(c, h))`` for ``inputs`` [B, T, I] (``time_major``: [T, B, I]).
-    Without ``initial_state`` the state starts at zero (in ``dtype`` or the dtype of ``inputs``).  On the HIP path
-    the returned ``c`` is fp32."""
+    """``tf.nn.dynamic_rnn``: ``(outputs, LSTMStateTuple(c, h))`` for ``inputs`` [B, T, I] (``time_major``: [T, B, I]);
+    for a ``GRUCell`` the state is one tensor [B, H], in the dtype of ``inputs``.  Without ``initial_state`` the state
+    starts at zero (in ``dtype`` or the dtype of ``inputs``).  On the HIP path the returned ``c`` is fp32."""
     from . import rnn
     from ..train import variables as V
-    if not isinstance(cell, LSTMCell):
-        raise TypeError("dynamic_rnn: only LSTMCell / BasicLSTMCell cells are implemented, got %r" % (cell,))
+    if not isinstance(cell, (LSTMCell, GRUCell)):
+        raise TypeError("dynamic_rnn: only LSTMCell / BasicLSTMCell / GRUCell cells are implemented, got %r" % (cell,))
     if inputs.dim() != 3:
         raise ValueError("dynamic_rnn: inputs must be rank 3, got %s" % (tuple(inputs.shape),))
     x = inputs if time_major else inputs.transpose(0, 1).contiguous()    # the kernels are time-major
     batch = x.shape[1]
     if initial_state is None:
         initial_state = cell.zero_state(batch, dtype or x.dtype, device=x.device)
+    if isinstance(cell, GRUCell):
+        from . import gru
+        with V.variable_scope(scope if scope is not None else "rnn"):
+            params = cell.variables(x.shape[2])
+        hs, h_t = gru.gru(x, *params, initial_state, sequence_length)
+        return (hs if time_major else hs.transpose(0, 1)), h_t
     c0, h0 = initial_state
     with V.variable_scope(scope if scope is not None else "rnn"):
         kernel, bias = cell.variables(x.shape[2])
