@@ -494,3 +494,27 @@ def add_n(ts):
 # ---------------------------------------------------------------------------
 from . import rnn_cell  # noqa: E402
 from .rnn_cell import bidirectional_dynamic_rnn, dynamic_rnn  # noqa: E402,F401
+
+
+def ctc_loss(labels, inputs, sequence_length, preprocess_collapse_repeated=False, ctc_merge_repeated=True,
+             ignore_longer_outputs_than_inputs=False, time_major=True, label_length=None):
+    """``tf.nn.ctc_loss``: fp32 [B], one loss per item, of unnormalised logits ``inputs`` [T, B, K] (``[B, T, K]`` with
+    ``time_major=False``; bf16 or fp32, the softmax is inside the op) with the blank as class ``K - 1``.
+
+    There is no SparseTensor here: ``labels`` is a dense integer ``[B, Lmax]`` tensor of values in ``[0, K - 1)`` and
+    ``label_length`` [B] is required (TF2's ``ctc_loss_v2`` form).  Item b uses the frames ``t < sequence_length[b]``
+    and its first ``label_length[b]`` labels; int32 device tensors of lengths are read by the kernels as they are, so
+    they may change in place between replays of a captured step.  An item without an alignment (more labels, plus
+    adjacent repeats, than frames; a label out of range) does not raise, since nothing is read on the host: its loss
+    is ``+inf``, or 0 with ``ignore_longer_outputs_than_inputs``, and its gradient exactly 0.  The gradient flows to
+    ``inputs`` only and is exactly 0 at the frames past an item's length, which are never read.  Reduce over the batch
+    with ``mdtf.ops.losses.reduce_rows``.  GPU tensors with ``Lmax <= 511`` run the HIP kernels of ``ops/ctc.py``.
+    """
+    if preprocess_collapse_repeated:
+        raise NotImplementedError("ctc_loss: preprocess_collapse_repeated=True is not implemented")
+    if not ctc_merge_repeated:
+        raise NotImplementedError("ctc_loss: ctc_merge_repeated=False is not implemented")
+    from . import ctc
+    if not time_major and inputs.dim() == 3:
+        inputs = inputs.transpose(0, 1)
+    return ctc.ctc_loss(inputs, labels, sequence_length, label_length, ignore_longer_outputs_than_inputs)
