@@ -18,6 +18,12 @@ calls first) and the replay is timed with device events ``--reps`` times (median
 units per block forced to every (gate launch, other launches) pair of 16 and 32, per step (a forward step is its two
 launches, a backward step two of its 2T + 1): what decides ``pick_u`` in csrc/gru.hip.
 
+``--lengths`` times per-row lengths (uniform random in [T/2, T], an int32 device tensor) and two directions.  Whole
+layer: ``full`` (no lengths, forward in time), ``lens``, ``bi`` (``gru.bigru``: a forward and a reverse GRU in the
+same launches) and ``two calls`` (the same pair as ``gru.gru`` + ``gru.gru(reverse=True)``) on the HIP path, ``lens``
+and ``bi`` also as the PyTorch loop.  Recurrences alone: ``mdtf_gru_fwd`` / ``mdtf_gru_bwd`` (the full-length
+kernels) against ``mdtf_gru_fwd_seq`` / ``mdtf_gru_bwd_seq`` without lengths, with them, and with two directions.
+
 ``--trace T,B,H`` runs the recurrences a few times with both block widths and nothing else, as the program of a
 kernel-trace profiler run, which gives the time of each of the four step kernels.
 """
@@ -87,6 +93,95 @@ def recurrence(t, b, h, gen):
             lambda: N.check(N.fn("mdtf_gru_bwd")(*[P(v) for v in ba], t, b, h, gru.BF16, N.stream_ptr()), "gru_bwd"))
 
 
+def _direction(h, gen):
+    """``(gates kernel, gates bias, candidate kernel, candidate bias, h0)`` with fp32 gradient slots, I = H."""
+    out = []
+    for cols in (2 * h, h):
+        k = (torch.randn((2 * h, cols), generator=gen) * (2 * h) ** -0.5).cuda().bfloat16().requires_grad_(True)
+        bias = torch.zeros(cols, device="cuda", dtype=torch.bfloat16).requires_grad_(True)
+        k._mdtf_var, bias._mdtf_var = _Slot(torch.zeros((2 * h, cols), device="cuda")), _Slot(torch.zeros(cols, device="cuda"))
+        out += [k, bias]
+    return out
+
+
+def lengths_passes(t, b, h, lens, gen):
+    """``{variant: {pass: fn}}`` of the whole layer with lengths and two directions (``--lengths``)."""
+    from mdtf.ops import gru
+    x = torch.randn((t, b, h), generator=gen).cuda().bfloat16().requires_grad_(True)
+    fw, bw = _direction(h, gen), _direction(h, gen)
+    h0 = torch.zeros((b, h), device="cuda", dtype=torch.bfloat16)
+    dhs = torch.randn((t, b, h), generator=gen).cuda().bfloat16()
+    calls = {"full": lambda: [gru.gru(x, *fw, h0)[0]],
+             "lens": lambda: [gru.gru(x, *fw, h0, lens)[0]],
+             "bi": lambda: [r[0] for r in gru.bigru(x, fw + [h0], bw + [h0], lens)],
+             "two calls": lambda: [gru.gru(x, *fw, h0, lens)[0], gru.gru(x, *bw, h0, lens, reverse=True)[0]]}
+
+    def passes(call, leaves):
+        def fwd():
+            with torch.no_grad():
+                return call()[0]
+
+        def both():
+            ys = call()
+            return torch.autograd.grad(ys, leaves, [dhs] * len(ys))[0]
+        return {"fwd": fwd, "fwd+bwd": both}
+    out = {k: passes(f, [x] + fw + (bw if k in ("bi", "two calls") else [])) for k, f in calls.items()}
+    for k in ("lens", "bi"):
+        out[k + " loop"] = {which: with_mode("torch", f) for which, f in out[k].items()}
+    return out
+
+
+def seq_recurrence(t, b, h, lens, ndir, gen):
+    """The length-aware recurrences alone through the entry points: ``(forward, backward)``."""
+    from mdtf.ops import _native as N, gru, rnn
+    new = lambda *shape, dtype=torch.bfloat16, scale=1.0: (torch.randn(shape, generator=gen) * scale).cuda().to(dtype)
+    f32 = torch.float32
+    xg, fwd, bwd = new(t, b, 3 * h * ndir), [], []
+    for d in range(ndir):
+        z = dict(wg=new(h, 2 * h, scale=(2 * h) ** -0.5), wc=new(h, h, scale=(2 * h) ** -0.5), wt=new(3 * h * h),
+                 h0=new(b, h, scale=0.5), hs=new(t, b, h), hf=new(t, b, h, dtype=f32), rh=new(t, b, h),
+                 gates=new(t, b, 3 * h), h_fin=new(b, h), dhs=new(t, b, h), carry=new(b, h, dtype=f32), dg=new(t, b, 3 * h))
+        z["h0f"] = z["h0"].float()
+        fwd.append([xg[:, :, 3 * h * d:]] + [z[k] for k in ("wg", "wc", "wt", "h0", "h0f", "hs", "hf", "rh", "gates", "h_fin")])
+        bwd.append([z[k] for k in ("wg", "wc", "gates", "hf", "h0f", "dhs", "carry", "dg")])
+    rev = 0b10 if ndir == 2 else 0
+    return (lambda: N.check(N.fn("mdtf_gru_fwd_seq")(rnn._table(fwd), ndir, rev, N.ptr(lens), t, b, h, 3 * h * ndir,
+                                                     gru.BF16, N.stream_ptr()), "gru_fwd_seq"),
+            lambda: N.check(N.fn("mdtf_gru_bwd_seq")(rnn._table(bwd), ndir, rev, N.ptr(lens), t, b, h, gru.BF16,
+                                                     N.stream_ptr()), "gru_bwd_seq"))
+
+
+def _timed(variants, args):
+    """``{variant: {"us", "us_min", "us_max"}}``, the variants alternating ``args.rounds`` times."""
+    times = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for key, f in variants.items():
+            times[key].append(graph_time(f, args.iters, args.reps))
+    return {k: {"us": round(sorted(x[0] for x in ts)[len(ts) // 2], 1), "us_min": round(min(x[1] for x in ts), 1),
+                "us_max": round(max(x[2] for x in ts), 1)} for k, ts in times.items()}
+
+
+def lengths_probe(args, gen):
+    for t, b, h in SHAPES:
+        lens = torch.randint(t // 2, t + 1, (b,), generator=gen).to(torch.int32).cuda()
+        base = {"T": t, "B": b, "H": h, "mean_length": round(float(lens.float().mean()), 1), "iters": args.iters,
+                "reps": args.reps, "rounds": args.rounds}
+        layer = lengths_passes(t, b, h, lens, gen)
+        for which in ("fwd", "fwd+bwd"):
+            rec = dict(base, probe="gru_lengths", **{"pass": which})
+            rec.update(_timed({k: v[which] for k, v in layer.items()}, args))
+            rec["loop_over_native"] = {k: round(rec[k + " loop"]["us"] / rec[k]["us"], 2) for k in ("lens", "bi")}
+            print(json.dumps(rec), flush=True)
+        del layer
+        old = recurrence(t, b, h, gen)
+        seq = {"seq": seq_recurrence(t, b, h, None, 1, gen), "seq lens": seq_recurrence(t, b, h, lens, 1, gen),
+               "seq bi lens": seq_recurrence(t, b, h, lens, 2, gen)}
+        for i, which in enumerate(("fwd", "bwd")):
+            rec = dict(base, probe="gru_lengths_recurrence", **{"pass": which})
+            rec.update(_timed(dict({"full-length kernels": old[i]}, **{k: v[i] for k, v in seq.items()}), args))
+            print(json.dumps(rec), flush=True)
+
+
 def force_units(gate, cand):
     from mdtf.ops import _native as N
     N.check(N.fn("mdtf_gru_force_units")(gate, cand), "gru_force_units")
@@ -131,6 +226,7 @@ def main():
     p.add_argument("--reps", type=int, default=7, help="timed replays per measurement")
     p.add_argument("--rounds", type=int, default=3, help="alternations of the variants")
     p.add_argument("--units", action="store_true", help="time the recurrences alone with forced units per block")
+    p.add_argument("--lengths", action="store_true", help="time per-row lengths and two directions")
     p.add_argument("--trace", default=None, metavar="T,B,H", help="run the recurrences only (for a kernel trace)")
     args = p.parse_args()
     sys.argv = sys.argv[:1]                        # mdtf's own flags parse the command line on first use
@@ -144,6 +240,8 @@ def main():
         return trace_program(args.trace, gen)
     if args.units:
         return units_probe(args, gen)
+    if args.lengths:
+        return lengths_probe(args, gen)
     for t, b, h in SHAPES:
         ours, lib = mdtf_passes(t, b, h, gen), library_passes(t, b, h, gen)
         for which in ("fwd", "fwd+bwd"):

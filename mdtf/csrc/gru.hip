@@ -44,6 +44,15 @@
 // No kernel spans time steps, no block waits for another, no float atomics: every (row, unit) of every output has
 // exactly one owner lane in exactly one block per launch.  The entry points allocate nothing and loop over t
 // themselves, so they replay inside a hipGraph.
+//
+// gru_gate_fwd / gru_cand_fwd / gru_bwd_a / gru_bwd_b run full-length, forward-in-time sequences (mdtf_gru_fwd /
+// mdtf_gru_bwd); gru_gate_seq / gru_cand_seq / gru_bwd_a_seq / gru_bwd_b_seq further down add per-row lengths, the
+// reverse direction and two directions per launch (mdtf_gru_fwd_seq / mdtf_gru_bwd_seq) on the same GEMM, reduction
+// and cell arithmetic, and give the same bits where every row has length T.  All of the above holds for them; the
+// comment in front of them says how liveness, the previous-state operand and the dG rule carry over.  The lengths
+// are read by the kernels only, so results are bitwise repeatable and a captured call replays after the lengths
+// change in place.  A full-length launch of the seq kernels costs 0.6 to 0.9 us more than its plain counterpart
+// (profiles/gru.md, "Lengths and two directions"), which is why the plain ones stay.
 #include "rnn_tile.h"
 
 namespace {
@@ -238,6 +247,292 @@ __global__ __launch_bounds__(kWaves* kWave) void gru_bwd_b(BwdArgs a) {
   }
 }
 
+// ---- per-row lengths and direction (tf.nn.dynamic_rnn(sequence_length=), a forward plus a reverse GRU) --------------
+//
+// Row b is live at step t iff t < clamp(lens[b], 0, T); a dead row emits zeros and keeps its state.  A reverse
+// direction visits t = T - 1 .. 0 under the same rule (TF's reverse_sequence -> GRU -> reverse_sequence with nothing
+// reversed in memory): its padding steps come first and leave the initial state in place.  The state is never copied
+// through dead steps: the A operand of skinny_gemm is per lane (a lane owns row l % 16), so each live row reads
+// hs[the step visited before] / hf[the same], or h0 / h0f at its first visited live step (t = 0 forward, t = len - 1
+// reverse), and a dead row is read as zeros.  Both launches of a step derive liveness from `lens` alone, so the fp32
+// u that hf[t] hands from the gate launch to the candidate launch exists exactly where the candidate launch reads it.
+// A 16-row tile with no live row skips its GEMM (the ballot is the same in every wave: a wave's lanes cover all 16
+// rows) and only writes zeros.  Dead (t, b) of hs, hf, rh, gates and dG are written as zeros, because the caller
+// multiplies whole [T * B, .] buffers into the weight gradients and dx.  blockIdx.z is the direction; launch s runs
+// step s of a forward direction and step T - 1 - s of a reverse one.  `lens` is read here and nowhere on the host;
+// null: every row has length T.
+//
+// dG in both directions.  With tn the step the forward visited after t (t + 1 forward, t - 1 reverse), gru_bwd_a_seq
+// at step t reads the r | u columns of dG[tn] and writes the u | c columns of dG[t], and tn != t; its closing launch
+// reads, per row, the r | u columns of dG[that row's first visited live step] and writes no dG at all.
+// gru_bwd_b_seq reads the c columns of dG[t] and writes its r columns.  Each direction has a dG of its own.  So in
+// either direction a launch reads only columns or steps of dG that none of its blocks writes.
+
+constexpr int kDirs = 2;
+
+__device__ __forceinline__ int row_len(const int* lens, int row, int T) {
+  return lens != nullptr ? min(max(lens[row], 0), T) : T;
+}
+
+struct SeqFwdDir {
+  const bf16_t* xg;      // [T, B, ldx]: this direction's 3H columns of the input half
+  const bf16_t* wt_g;    // packed recurrent weights of the gate launch
+  const bf16_t* wt_c;    // ... of the candidate launch
+  const bf16_t* h0;      // [B, H]
+  const float* h0f;      // [B, H], the same state in fp32
+  bf16_t* hs;            // [T, B, H], zeros at dead (t, b), as are hf, rh and gates
+  float* hf;             // [T, B, H]
+  bf16_t* rh;            // [T, B, H]
+  bf16_t* gates;         // [T, B, 3H]
+  bf16_t* h_fin;         // [B, H]: hs at the row's last visited live step (h0 for length 0)
+  int reverse;
+};
+
+struct SeqFwdArgs {
+  SeqFwdDir d[kDirs];
+  const int* lens;       // [B] or null
+  int s, T, B, H, ldx;
+};
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void gru_gate_seq(SeqFwdArgs a) {
+  constexpr int NT = U / 16, NB = 2 * NT;
+  __shared__ float red[kWaves * NB * 4 * kWave];
+  const SeqFwdDir& d = a.d[blockIdx.z];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+  const bool rev = d.reverse != 0;
+  const int t = rev ? a.T - 1 - a.s : a.s, tp = rev ? t + 1 : t - 1;     // tp: the step visited before this one
+  const int64_t sh = static_cast<int64_t>(a.B) * H;
+
+  const int arow = row0 + lr;
+  bool a_ok = false;
+  const bf16_t* a_lane = d.h0 + lk;
+  if (arow < a.B) {
+    const int len = row_len(a.lens, arow, a.T);
+    a_ok = t < len;
+    const bool first = rev ? t + 1 >= len : t == 0;
+    a_lane = (first ? d.h0 : d.hs + tp * sh) + static_cast<int64_t>(arow) * H + lk;
+  }
+  float pre[NB];
+  if (__ballot(a_ok) != 0) {                       // block-uniform: some row of the tile is live
+    float4v acc[NB];
+#pragma unroll
+    for (int n = 0; n < NB; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+    const bf16_t* b_lane = d.wt_g + (static_cast<int64_t>(slice) * 2 * U + lr) * H + lk;
+    skinny_gemm<NB>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * H, H / kStep, wave, acc);
+    reduce_waves<NB>(red, acc, wave, lane, pre);
+  }
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+  const int len = row_len(a.lens, row, a.T);
+  const bool live = t < len, first = rev ? t + 1 >= len : t == 0;
+  const float* h_prev = first ? d.h0f : d.hf + tp * sh;
+  const bf16_t* xg = d.xg + (static_cast<int64_t>(t) * a.B + row) * a.ldx;
+  bf16_t* gates = d.gates + t * 3 * sh;
+  bf16_t* rh = d.rh + t * sh;
+  float* hf = d.hf + t * sh;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 3 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    if (!live) {
+      gates[g0] = gates[g0 + H] = rh[s0] = f2bf(0.f);
+      continue;
+    }
+    const float r = sigmoid_fast(pre[nt] + bf2f(xg[unit]));
+    const float u = sigmoid_fast(pre[NT + nt] + bf2f(xg[unit + H]));
+    gates[g0] = f2bf(r);
+    gates[g0 + H] = f2bf(u);
+    rh[s0] = f2bf(r * h_prev[s0]);
+    hf[s0] = u;                                    // fp32, for the candidate launch of this step (see "The carry")
+  }
+}
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void gru_cand_seq(SeqFwdArgs a) {
+  constexpr int NT = U / 16;
+  __shared__ float red[kWaves * NT * 4 * kWave];
+  const SeqFwdDir& d = a.d[blockIdx.z];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+  const bool rev = d.reverse != 0;
+  const int t = rev ? a.T - 1 - a.s : a.s, tp = rev ? t + 1 : t - 1;
+  const int64_t sh = static_cast<int64_t>(a.B) * H;
+
+  const int arow = row0 + lr;
+  const bool a_ok = arow < a.B && t < row_len(a.lens, arow, a.T);
+  const bf16_t* a_lane = d.rh + t * sh + static_cast<int64_t>(a_ok ? arow : 0) * H + lk;
+  float pre[NT];
+  if (__ballot(a_ok) != 0) {                       // block-uniform
+    float4v acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+    const bf16_t* b_lane = d.wt_c + (static_cast<int64_t>(slice) * U + lr) * H + lk;
+    skinny_gemm<NT>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * H, H / kStep, wave, acc);
+    reduce_waves<NT>(red, acc, wave, lane, pre);
+  }
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+  const int len = row_len(a.lens, row, a.T);
+  const bool live = t < len, first = rev ? t + 1 >= len : t == 0, last = rev ? t == 0 : t + 1 == len;
+  const float* h_prev = first ? d.h0f : d.hf + tp * sh;
+  const bf16_t* xg = d.xg + (static_cast<int64_t>(t) * a.B + row) * a.ldx;
+  bf16_t* gates = d.gates + t * 3 * sh;
+  bf16_t* hs = d.hs + t * sh;
+  float* hf = d.hf + t * sh;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 3 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    if (!live) {
+      gates[g0 + 2 * H] = hs[s0] = f2bf(0.f);
+      hf[s0] = 0.f;
+      if (len == 0 && a.s == 0) d.h_fin[s0] = d.h0[s0];
+      continue;
+    }
+    const float c = tanh_fast(pre[nt] + bf2f(xg[unit + 2 * H]));
+    const float u = hf[s0];                        // left here in fp32 by the gate launch; h replaces it below
+    const float h = u * h_prev[s0] + (1.0f - u) * c;
+    hf[s0] = h;
+    hs[s0] = f2bf(h);
+    gates[g0 + 2 * H] = f2bf(c);
+    if (last) d.h_fin[s0] = f2bf(h);
+  }
+}
+
+struct SeqBwdDir {
+  const bf16_t* wg;       // gates/kernel[I:] [H, 2H]
+  const bf16_t* wc;       // candidate/kernel[I:] [H, H]
+  const bf16_t* gates;    // [T, B, 3H]
+  const float* hf;        // [T, B, H]
+  const float* h0f;       // [B, H]
+  const bf16_t* dhs;      // [T, B, H]
+  float* dh_carry;        // [B, H] fp32, in place; a dead row leaves it alone, which carries dL/dh_T to its last step
+  bf16_t* dg;             // dG [T, B, 3H], zeros at dead (t, b)
+  int reverse;
+};
+
+struct SeqBwdArgs {
+  SeqBwdDir d[kDirs];
+  const int* lens;
+  int s, T, B, H;         // s = T: the closing GEMM-only launch of gru_bwd_a_seq
+};
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void gru_bwd_a_seq(SeqBwdArgs a) {
+  constexpr int NT = U / 16;
+  __shared__ float red[kWaves * NT * 4 * kWave];
+  const SeqBwdDir& d = a.d[blockIdx.z];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+  const bool rev = d.reverse != 0, fin = a.s == a.T;
+  // the forward visited tp, t, tn in this order; this pass has written dG[tn] and writes dG[t]
+  const int t = rev ? a.s : a.T - 1 - a.s, tp = rev ? t + 1 : t - 1, tn = rev ? t - 1 : t + 1;
+  const int64_t sh = static_cast<int64_t>(a.B) * H;
+
+  const int arow = row0 + lr;
+  bool a_ok = false;
+  const bf16_t* a_lane = d.dg + lk;
+  if (arow < a.B) {
+    const int len = row_len(a.lens, arow, a.T);
+    // the closing launch reads dG of the row's first visited live step; a step reads dG[tn] where the row was live
+    a_ok = fin ? len > 0 : t < len && (rev ? t > 0 : t + 1 < len);
+    const int src = fin ? (rev ? len - 1 : 0) : tn;
+    if (a_ok) a_lane = d.dg + (src * sh + static_cast<int64_t>(arow) * H) * 3 + lk;
+  }
+  float dhr[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) dhr[nt] = 0.f;
+  if (__ballot(a_ok) != 0) {                       // block-uniform
+    float4v acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+    const bf16_t* b_lane = d.wg + static_cast<int64_t>(slice * U + lr) * 2 * H + lk;
+    skinny_gemm<NT>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * 2 * H, 2 * H / kStep, wave, acc);
+    reduce_waves<NT>(red, acc, wave, lane, dhr);
+  }
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+  const int len = row_len(a.lens, row, a.T);
+  const bool live = t < len, first = rev ? t + 1 >= len : t == 0;
+  // (the closing launch dereferences none of these)
+  const bf16_t* gates = d.gates + t * 3 * sh;
+  const float* h_prev = first ? d.h0f : d.hf + tp * sh;
+  const bf16_t* dh_out = d.dhs + t * sh;
+  bf16_t* dg = d.dg + t * 3 * sh;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 3 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    if (fin) {
+      if (len > 0) d.dh_carry[s0] += dhr[nt];      // a row of length 0 returns dL/dh_T as it came
+      continue;
+    }
+    if (!live) {
+      dg[g0 + H] = dg[g0 + 2 * H] = f2bf(0.f);
+      continue;
+    }
+    const float dh = d.dh_carry[s0] + dhr[nt] + bf2f(dh_out[s0]);
+    const float u = bf2f(gates[g0 + H]), c = bf2f(gates[g0 + 2 * H]);
+    dg[g0 + 2 * H] = f2bf(dh * (1.0f - u) * (1.0f - c * c));
+    dg[g0 + H] = f2bf(dh * (h_prev[s0] - c) * u * (1.0f - u));
+    d.dh_carry[s0] = dh * u;
+  }
+}
+
+template <int U>
+__global__ __launch_bounds__(kWaves* kWave) void gru_bwd_b_seq(SeqBwdArgs a) {
+  constexpr int NT = U / 16;
+  __shared__ float red[kWaves * NT * 4 * kWave];
+  const SeqBwdDir& d = a.d[blockIdx.z];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slice = blockIdx.x, row0 = blockIdx.y * kRows;
+  const int H = a.H, lr = lane & 15, lk = (lane >> 4) * 8;
+  const bool rev = d.reverse != 0;
+  const int t = rev ? a.s : a.T - 1 - a.s, tp = rev ? t + 1 : t - 1;
+  const int64_t sh = static_cast<int64_t>(a.B) * H;
+
+  const int arow = row0 + lr;
+  const bool a_ok = arow < a.B && t < row_len(a.lens, arow, a.T);
+  const bf16_t* a_lane = d.dg + (t * sh + static_cast<int64_t>(a_ok ? arow : 0) * H) * 3 + 2 * H + lk;
+  float drh[NT];
+  if (__ballot(a_ok) != 0) {                       // block-uniform
+    float4v acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = float4v{0.f, 0.f, 0.f, 0.f};
+    const bf16_t* b_lane = d.wc + static_cast<int64_t>(slice * U + lr) * H + lk;
+    skinny_gemm<NT>(a_lane, a_ok, b_lane, static_cast<int64_t>(16) * H, H / kStep, wave, acc);
+    reduce_waves<NT>(red, acc, wave, lane, drh);
+  }
+
+  const int row = row0 + (lane >> 4) * 4 + wave;
+  if (row >= a.B) return;
+  const int len = row_len(a.lens, row, a.T);
+  const bool live = t < len, first = rev ? t + 1 >= len : t == 0;
+  const bf16_t* gates = d.gates + t * 3 * sh;
+  const float* h_prev = first ? d.h0f : d.hf + tp * sh;
+  bf16_t* dg = d.dg + t * 3 * sh;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int unit = slice * U + nt * 16 + lr;
+    const int64_t g0 = static_cast<int64_t>(row) * 3 * H + unit, s0 = static_cast<int64_t>(row) * H + unit;
+    if (!live) {
+      dg[g0] = f2bf(0.f);
+      continue;
+    }
+    const float r = bf2f(gates[g0]);
+    dg[g0] = f2bf(drh[nt] * h_prev[s0] * r * (1.0f - r));
+    d.dh_carry[s0] += drh[nt] * r;
+  }
+}
+
 constexpr int kBf16 = 0;       // the dtype code of the entry points (1: fp32, refused)
 
 // Hidden units per block.  The candidate launch and both backward launches (one strip per 16 units) follow
@@ -355,6 +650,109 @@ MDTF_EXPORT int mdtf_gru_bwd(const void* wg, const void* wc, const void* gates, 
       gru_bwd_b<32><<<grid, kWaves * kWave, 0, st>>>(a);
     else
       gru_bwd_b<16><<<grid, kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+  }
+  return MDTF_OK;
+}
+
+// The length- and direction-aware recurrence of `ndir` (1 or 2) independent GRUs over the same T, B, H and the same
+// lengths, every step of all of them in the same two launches: ndir pack launches and 2T step launches on `st`.  Bit
+// d of `reverse`: direction d visits t = T - 1 .. 0.  `lens`: int32 [B] on the device (clamped to [0, T], never read
+// by the host) or null.  `tab` (host memory, read before the call returns) holds 11 pointers per direction, in the
+// order xg, wg, wc, wt, h0, h0f, hs, hf, rh, gates, h_fin: as mdtf_gru_fwd, except that xg rows are `ldx` elements
+// apart (the directions may be column ranges of one [T * B, ndir * 3H] product) and that h_fin [B, H] bf16 receives
+// the final state.  hs, hf, rh and gates are zero at dead (t, b).
+MDTF_EXPORT int mdtf_gru_fwd_seq(const void* const* tab, int ndir, int reverse, const int* lens, int T, int B, int H,
+                                 int ldx, int dtype, hipStream_t st) {
+  if (!supported(T, B, H, dtype)) return MDTF_EUNSUPPORTED;
+  if (!tab || ndir < 1 || ndir > kDirs || ldx < 3 * H || ldx % 8) return MDTF_EINVAL;
+  for (int i = 0; i < 11 * ndir; ++i)
+    if (!tab[i]) return MDTF_EINVAL;
+  const int Ug = units_gate(B, H), Uc = units_cand(B, H);
+  SeqFwdArgs a;
+  for (int d = 0; d < kDirs; ++d) {
+    const void* const* p = tab + 11 * (d < ndir ? d : 0);     // (an unused slot repeats direction 0; no block reads it)
+    bf16_t* wt_g = static_cast<bf16_t*>(const_cast<void*>(p[3]));
+    bf16_t* wt_c = wt_g + static_cast<int64_t>(2) * H * H;
+    if (d < ndir) {
+      gru_pack_w<<<dim3(3 * H / 32, H / 32), 256, 0, st>>>(static_cast<const bf16_t*>(p[1]),
+                                                           static_cast<const bf16_t*>(p[2]), wt_g, wt_c, H, Ug, Uc);
+      MDTF_LAUNCH_CHECK();
+    }
+    SeqFwdDir& q = a.d[d];
+    q.xg = static_cast<const bf16_t*>(p[0]);
+    q.wt_g = wt_g;
+    q.wt_c = wt_c;
+    q.h0 = static_cast<const bf16_t*>(p[4]);
+    q.h0f = static_cast<const float*>(p[5]);
+    q.hs = static_cast<bf16_t*>(const_cast<void*>(p[6]));
+    q.hf = static_cast<float*>(const_cast<void*>(p[7]));
+    q.rh = static_cast<bf16_t*>(const_cast<void*>(p[8]));
+    q.gates = static_cast<bf16_t*>(const_cast<void*>(p[9]));
+    q.h_fin = static_cast<bf16_t*>(const_cast<void*>(p[10]));
+    q.reverse = (reverse >> d) & 1;
+  }
+  a.lens = lens;
+  a.T = T;
+  a.B = B;
+  a.H = H;
+  a.ldx = ldx;
+  const unsigned tiles = static_cast<unsigned>(ceil_div(B, kRows));
+  for (a.s = 0; a.s < T; ++a.s) {
+    if (Ug == 32)
+      gru_gate_seq<32><<<dim3(H / 32, tiles, ndir), kWaves * kWave, 0, st>>>(a);
+    else
+      gru_gate_seq<16><<<dim3(H / 16, tiles, ndir), kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+    if (Uc == 32)
+      gru_cand_seq<32><<<dim3(H / 32, tiles, ndir), kWaves * kWave, 0, st>>>(a);
+    else
+      gru_cand_seq<16><<<dim3(H / 16, tiles, ndir), kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+  }
+  return MDTF_OK;
+}
+
+// Its backward: 2T + 1 launches on `st`, the last one the GEMM-only launch that turns the carry into dL/dh_0.  `tab`:
+// 8 pointers per direction, in the order wg, wc, gates, hf, h0f, dhs, dh_carry, dg, as mdtf_gru_bwd.  dg is zero at
+// dead (t, b); dh_carry of a row of length 0 is returned as it came.
+MDTF_EXPORT int mdtf_gru_bwd_seq(const void* const* tab, int ndir, int reverse, const int* lens, int T, int B, int H,
+                                 int dtype, hipStream_t st) {
+  if (!supported(T, B, H, dtype)) return MDTF_EUNSUPPORTED;
+  if (!tab || ndir < 1 || ndir > kDirs) return MDTF_EINVAL;
+  for (int i = 0; i < 8 * ndir; ++i)
+    if (!tab[i]) return MDTF_EINVAL;
+  const int U = units_cand(B, H);
+  SeqBwdArgs a;
+  for (int d = 0; d < kDirs; ++d) {
+    const void* const* p = tab + 8 * (d < ndir ? d : 0);
+    SeqBwdDir& q = a.d[d];
+    q.wg = static_cast<const bf16_t*>(p[0]);
+    q.wc = static_cast<const bf16_t*>(p[1]);
+    q.gates = static_cast<const bf16_t*>(p[2]);
+    q.hf = static_cast<const float*>(p[3]);
+    q.h0f = static_cast<const float*>(p[4]);
+    q.dhs = static_cast<const bf16_t*>(p[5]);
+    q.dh_carry = static_cast<float*>(const_cast<void*>(p[6]));
+    q.dg = static_cast<bf16_t*>(const_cast<void*>(p[7]));
+    q.reverse = (reverse >> d) & 1;
+  }
+  a.lens = lens;
+  a.T = T;
+  a.B = B;
+  a.H = H;
+  const dim3 grid(H / U, static_cast<unsigned>(ceil_div(B, kRows)), ndir);
+  for (a.s = 0; a.s <= T; ++a.s) {
+    if (U == 32)
+      gru_bwd_a_seq<32><<<grid, kWaves * kWave, 0, st>>>(a);
+    else
+      gru_bwd_a_seq<16><<<grid, kWaves * kWave, 0, st>>>(a);
+    MDTF_LAUNCH_CHECK();
+    if (a.s == T) break;
+    if (U == 32)
+      gru_bwd_b_seq<32><<<grid, kWaves * kWave, 0, st>>>(a);
+    else
+      gru_bwd_b_seq<16><<<grid, kWaves * kWave, 0, st>>>(a);
     MDTF_LAUNCH_CHECK();
   }
   return MDTF_OK;

@@ -283,13 +283,43 @@ def lstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, initial_st
                            time_major=time_major, scope=layer_name)
 
 
-def gru(layer_name, x, num_units, time_major=False, initial_state=None, sequence_length=None):
+def _gru_direction(scope, xt, num_units, initial_state):
+    """``(gates kernel, gates bias, candidate kernel, candidate bias, h0)`` of a GRU over time-major ``xt`` with its
+    variables under ``scope``."""
+    cell = ops.rnn_cell.GRUCell(num_units)
+    with V.variable_scope(scope):
+        params = cell.variables(xt.shape[2])
+    if initial_state is None:
+        initial_state = cell.zero_state(xt.shape[1], xt.dtype, device=xt.device)
+    return params + (initial_state,)
+
+
+def gru(layer_name, x, num_units, time_major=False, initial_state=None, sequence_length=None, reverse=False):
     """One GRU layer over ``x`` [B, T, I] (``time_major``: [T, B, I]): ``(outputs, state [B, num_units])`` with the
     variables ``<layer_name>/gru_cell/gates/{kernel,bias}`` and ``.../candidate/{kernel,bias}``.  Stack layers by
-    calling it again on the outputs.  ``sequence_length`` [B]: past its length a row emits zeros and keeps its state."""
-    cell = ops.rnn_cell.GRUCell(num_units)
-    return ops.dynamic_rnn(cell, x, sequence_length=sequence_length, initial_state=initial_state,
-                           time_major=time_major, scope=layer_name)
+    calling it again on the outputs.  ``sequence_length`` [B]: past its length a row emits zeros and keeps its state.
+    ``reverse``: row b is read from ``sequence_length[b] - 1`` down to 0; the outputs stay in the time order of ``x``."""
+    if not reverse:
+        return ops.dynamic_rnn(ops.rnn_cell.GRUCell(num_units), x, sequence_length=sequence_length,
+                               initial_state=initial_state, time_major=time_major, scope=layer_name)
+    from ..ops import gru as G
+    xt = x if time_major else x.transpose(0, 1).contiguous()
+    hs, h_t = G.gru(xt, *_gru_direction(layer_name, xt, num_units, initial_state), sequence_length, reverse=True)
+    return (hs if time_major else hs.transpose(0, 1)), h_t
+
+
+def bigru(layer_name, x, num_units, time_major=False, sequence_length=None):
+    """One bidirectional GRU layer over ``x``: ``(outputs, (state_fw, state_bw))``, the outputs of the two directions
+    concatenated to ``2 * num_units`` features, with the variables
+    ``<layer_name>/fw/gru_cell/{gates,candidate}/{kernel,bias}`` and ``<layer_name>/bw/...``, the names TF's
+    ``bidirectional_dynamic_rnn`` gives them."""
+    from ..ops import gru as G
+    xt = x if time_major else x.transpose(0, 1).contiguous()
+    with V.variable_scope(layer_name):
+        fw, bw = (_gru_direction(d, xt, num_units, None) for d in ("fw", "bw"))
+    (hs_fw, h_fw), (hs_bw, h_bw) = G.bigru(xt, fw, bw, sequence_length)
+    out = torch.cat([hs_fw, hs_bw], -1)
+    return (out if time_major else out.transpose(0, 1)), (h_fw, h_bw)
 
 
 def bilstm(layer_name, x, num_units, forget_bias=1.0, time_major=False, sequence_length=None):

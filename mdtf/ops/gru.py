@@ -7,22 +7,35 @@ The cell is TF's ``GRUCell``, which applies the reset gate before the candidate 
     c     = tanh([x_t, r * h_{t-1}] @ cand_kernel + cand_bias)
     h_t   = u * h_{t-1} + (1 - u) * c
 
-The HIP path runs for GPU tensors in bf16 with ``H % 32 == 0``, full length, forward in time.  The input half
-``xg = x @ [gates_kernel[:I] | cand_kernel[:I]] + [gates_bias | cand_bias]`` over all ``T * B`` rows is one dense
-forward; the recurrence is two launches per step (``r``, ``u`` and ``r * h``; then the candidate and the update), all
-enqueued by one call of ``mdtf_gru_fwd``, and ``2T + 1`` launches of ``mdtf_gru_bwd`` backwards.  The state is carried
-in fp32 inside the call (``h`` is a leaky integrator: a bf16 carry loses the update where ``u`` is near 1); ``hs``, and
-with it the returned state, are its bf16 rounding, so ``h_T`` is bit for bit ``hs[-1]``.  Both kernel gradients and
-both bias gradients are ``gemm.wgrad_into`` on the row ranges of the variables' fp32 gradient slots when there are
-any, and ``dx`` is the dense data gradient over ``[gates_kernel[:I] | cand_kernel[:I]]``.
+``sequence_length`` [B]: row b is live at step t iff ``t < sequence_length[b]``; a dead row emits zeros and keeps its
+state, as TF does.  ``reverse``: the same recurrence visits ``t = T - 1 .. 0`` under the same rule, which is TF's
+``reverse_sequence`` -> GRU -> ``reverse_sequence`` with no tensor reversed.
+
+The HIP path runs for GPU tensors in bf16 with ``H % 32 == 0``, with or without lengths, in either direction, and for
+two directions at once (:func:`bigru`).  The input half ``xg = x @ [gates_kernel[:I] | cand_kernel[:I]] + [gates_bias |
+cand_bias]`` over all ``T * B`` rows is one dense forward (one product over ``[I, 6H]`` for two directions); the
+recurrence is two launches per step (``r``, ``u`` and ``r * h``; then the candidate and the update), both directions
+in the same launches, all enqueued by one call of ``mdtf_gru_fwd_seq``, and ``2T + 1`` launches of
+``mdtf_gru_bwd_seq`` backwards.  The lengths are an int32 device tensor that only the kernels read: nothing here reads
+them on the host, so they may change between replays of a captured step.  The state is carried in fp32 inside the
+call (``h`` is a leaky integrator: a bf16 carry loses the update where ``u`` is near 1); ``hs``, and with it the
+returned state, are its bf16 rounding, so ``h_T`` has the bits of ``hs`` at each row's last visited live step
+(``hs[-1]`` on a full-length forward call, ``h0`` for length 0).  Dead ``(t, b)`` of every saved buffer and of ``dG``
+are zeros, so the whole ``[T * B, .]`` buffers go into the products: both kernel gradients and both bias gradients are
+``gemm.wgrad_into`` on the row ranges of the variables' fp32 gradient slots when there are any (the recurrent rows of
+the gates kernel against ``rnn._h_prev``, those of the candidate kernel against ``r * h_prev``), and ``dx`` is the
+dense data gradient over ``[gates_kernel[:I] | cand_kernel[:I]]``, the second direction's added into the first's.
 
 Every other case runs :func:`gru_loop`, the definition as a PyTorch loop with fp32 gate math and an fp32 carry: CPU
-tensors, ``MDTF_KERNELS=torch`` (the comparator), fp32 activations, other ``H``, and any call with
-``sequence_length``.  Not here: the reset-after (Keras / cuDNN) cell, vanilla cells and multi-cell wrappers.
+tensors, ``MDTF_KERNELS=torch`` (the comparator), fp32 activations and other ``H``.  A single forward-in-time call
+without lengths runs ``mdtf_gru_fwd`` / ``mdtf_gru_bwd``, the same recurrence without the length and direction logic:
+the same bits, a little faster per step.  Not here: the reset-after (Keras / cuDNN)
+cell, vanilla cells and multi-cell wrappers.
 """
 import torch
 
 from . import _native as N
+from . import rnn
 from ..train import variables as V
 
 BF16 = 0        # dtype codes of the entry points (the kernels take only bf16)
@@ -31,13 +44,15 @@ N.register("mdtf_gru_units", [N.I] * 4)
 N.register("mdtf_gru_force_units", [N.I] * 2)
 N.register("mdtf_gru_fwd", [N.P] * 10 + [N.I] * 4 + [N.P])
 N.register("mdtf_gru_bwd", [N.P] * 8 + [N.I] * 4 + [N.P])
+N.register("mdtf_gru_fwd_seq", [N.P, N.I, N.I, N.P] + [N.I] * 5 + [N.P])
+N.register("mdtf_gru_bwd_seq", [N.P, N.I, N.I, N.P] + [N.I] * 4 + [N.P])
 
 
 def native_ok(x, cand_kernel, h0, sequence_length=None):
-    """Whether the HIP kernels take this call (else the PyTorch loop runs)."""
+    """Whether the HIP kernels take this call (else the PyTorch loop runs); lengths do not matter."""
     t, b, i = x.shape
     h = cand_kernel.shape[1]
-    return (sequence_length is None and N.use_native(x) and x.dtype == torch.bfloat16 and h % 32 == 0 and h >= 32
+    return (N.use_native(x) and x.dtype == torch.bfloat16 and h % 32 == 0 and h >= 32
             and t >= 1 and b >= 1 and i >= 1 and h0.is_cuda and b * 3 * h < (1 << 31) and b <= 16 * 65535)
 
 
@@ -47,9 +62,10 @@ def units_per_block(t, b, h):
     return code & 0xFF, code >> 8
 
 
-def gru_loop(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length=None):
+def gru_loop(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length=None, reverse=False):
     """The definition as a loop over t: ``(hs [T, B, H], h_T)``.  Gate math and the carried state in fp32, ``hs`` and
-    ``h_T`` in the dtype of ``x``.  ``sequence_length`` [B]: at ``t >= length`` a row emits zeros and keeps its state."""
+    ``h_T`` in the dtype of ``x``.  ``sequence_length`` [B]: at ``t >= length`` a row emits zeros and keeps its state.
+    ``reverse``: t runs from ``T - 1`` down to 0 (the padding steps first, leaving the initial state in place)."""
     t_n, b_n, i_n = x.shape
     h_n = cand_kernel.shape[1]
     wg, wc = gates_kernel.to(x.dtype), cand_kernel.to(x.dtype)
@@ -59,19 +75,19 @@ def gru_loop(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_l
     h = h0.float()
     if sequence_length is not None:
         sequence_length = torch.as_tensor(sequence_length, device=x.device).reshape(b_n, 1)
-    outs = []
-    for t in range(t_n):
+    outs = [None] * t_n
+    for t in (range(t_n - 1, -1, -1) if reverse else range(t_n)):
         hb = h.to(x.dtype).float()                                      # the products see h in the dtype of x
         r, u = torch.sigmoid(xg[t, :, :2 * h_n] + torch.matmul(hb, wgh)).split(h_n, 1)
         c = torch.tanh(xg[t, :, 2 * h_n:] + torch.matmul((r * h).to(x.dtype).float(), wch))
         h_new = u * h + (1.0 - u) * c
         if sequence_length is None:
             h = h_new
-            outs.append(h.to(x.dtype))
+            outs[t] = h.to(x.dtype)
         else:
             live = sequence_length > t
             h = torch.where(live, h_new, h)
-            outs.append(torch.where(live, h_new, torch.zeros_like(h_new)).to(x.dtype))
+            outs[t] = torch.where(live, h_new, torch.zeros_like(h_new)).to(x.dtype)
     return torch.stack(outs, 0), h.to(x.dtype)
 
 
@@ -80,68 +96,107 @@ def _aligned(*ts):
 
 
 class _GRU(torch.autograd.Function):
+    """``ndir`` (1 or 2) GRUs over the same ``x`` and lengths, direction d reversed where bit d of ``reverse`` is set;
+    ``params``: ``gates_kernel, gates_bias, cand_kernel, cand_bias, h0`` per direction; returns ``hs, h_T`` per
+    direction."""
 
     @staticmethod
-    def forward(ctx, x, gk, gb, ck, cb, h0):
+    def forward(ctx, x, lens, reverse, *params):
         from . import gemm
+        ndir = len(params) // 5
         t_n, b_n, i_n = x.shape
-        h_n = ck.shape[1]
+        h_n = params[2].shape[1]
         dev = x.device
-        ctx.like = (gk, gb, ck, cb, h0)
-        ctx.sinks = [V.grad_sink(p) for p in (gk, gb, ck, cb)]
         x = x.contiguous()
-        gk, ck = gk.contiguous(), ck.contiguous()
-        h0b, h0f = h0.to(torch.bfloat16).contiguous(), h0.float().contiguous()
-        # the input halves of r | u | c, biases included: one product, [T * B, 3H]
-        xg = gemm.dense_multi(x.view(t_n * b_n, i_n), [gk[:i_n], ck[:i_n]], [gb.to(x.dtype), cb.to(x.dtype)]).contiguous()
         new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-        hs, rh = new((t_n, b_n, h_n), torch.bfloat16), new((t_n, b_n, h_n), torch.bfloat16)
-        hf, gates = new((t_n, b_n, h_n), torch.float32), new((t_n, b_n, 3 * h_n), torch.bfloat16)
-        wt = new(3 * h_n * h_n, torch.bfloat16)
-        if not _aligned(xg, gk[i_n:], ck[i_n:], h0b, h0f):
-            raise RuntimeError("mdtf gru: operands must be 16-byte aligned")
-        N.check(N.fn("mdtf_gru_fwd")(N.ptr(xg), N.ptr(gk[i_n:]), N.ptr(ck[i_n:]), N.ptr(wt), N.ptr(h0b), N.ptr(h0f),
-                                     N.ptr(hs), N.ptr(hf), N.ptr(rh), N.ptr(gates), t_n, b_n, h_n, BF16,
-                                     N.stream_ptr()), "gru_fwd")
-        ctx.save_for_backward(x, gk, ck, h0b, h0f, hs, hf, rh, gates)
-        return hs, hs[-1].clone()
+        ws, bs = [], []
+        for d in range(ndir):
+            gk, gb, ck, cb = params[5 * d:5 * d + 4]
+            ws += [gk[:i_n], ck[:i_n]]
+            bs += [gb.to(x.dtype), cb.to(x.dtype)]
+        # the input halves of r | u | c of all directions, biases included: one product, [T * B, ndir * 3H]
+        xg = gemm.dense_multi(x.view(t_n * b_n, i_n), ws, bs).contiguous()
+        rows, saved, outs = [], [], []
+        for d in range(ndir):
+            gk, ck = params[5 * d].contiguous(), params[5 * d + 2].contiguous()
+            h0 = params[5 * d + 4]
+            h0b, h0f = h0.to(torch.bfloat16).contiguous(), h0.float().contiguous()
+            hs, rh = new((t_n, b_n, h_n), torch.bfloat16), new((t_n, b_n, h_n), torch.bfloat16)
+            hf, gates = new((t_n, b_n, h_n), torch.float32), new((t_n, b_n, 3 * h_n), torch.bfloat16)
+            wt, h_fin = new(3 * h_n * h_n, torch.bfloat16), new((b_n, h_n), torch.bfloat16)
+            if not _aligned(gk[i_n:], ck[i_n:], h0b, h0f) or xg.data_ptr() % 16:
+                raise RuntimeError("mdtf gru: operands must be 16-byte aligned")
+            rows.append((xg[:, 3 * h_n * d:], gk[i_n:], ck[i_n:], wt, h0b, h0f, hs, hf, rh, gates, h_fin))
+            saved += [gk, ck, h0b, h0f, hs, hf, rh, gates]
+            outs += [hs, h_fin]
+        # full length, forward in time, one direction: the kernels without the length and direction logic, which are
+        # 1.2 to 1.8 us a step faster (profiles/gru.md) and give the same bits
+        ctx.plain = lens is None and ndir == 1 and not reverse
+        if ctx.plain:
+            N.check(N.fn("mdtf_gru_fwd")(*[N.ptr(z) for z in rows[0][:10]], t_n, b_n, h_n, BF16, N.stream_ptr()),
+                    "gru_fwd")
+            outs[1].copy_(outs[0][-1])
+        else:
+            N.check(N.fn("mdtf_gru_fwd_seq")(rnn._table(rows), ndir, reverse, N.ptr(lens), t_n, b_n, h_n, xg.shape[1],
+                                             BF16, N.stream_ptr()), "gru_fwd_seq")
+        ctx.save_for_backward(x, lens, *saved)
+        ctx.reverse, ctx.like = reverse, params
+        ctx.sinks = [[V.grad_sink(p) for p in params[5 * d:5 * d + 4]] for d in range(ndir)]
+        return tuple(outs)
 
     @staticmethod
-    def backward(ctx, dhs, dh_t):
+    def backward(ctx, *grads):
         from . import gemm
-        x, gk, ck, h0b, h0f, hs, hf, rh, gates = ctx.saved_tensors
+        x, lens = ctx.saved_tensors[:2]
+        saved = ctx.saved_tensors[2:]
+        ndir = len(saved) // 8
         t_n, b_n, i_n = x.shape
-        h_n = ck.shape[1]
+        h_n = saved[1].shape[1]
         dev = x.device
-        dhs = dhs.to(torch.bfloat16).contiguous()
-        carry = dh_t.float().clone()                                    # dL/dh_T in, dL/dh_0 out
-        dg = torch.empty((t_n, b_n, 3 * h_n), dtype=torch.bfloat16, device=dev)
-        N.check(N.fn("mdtf_gru_bwd")(N.ptr(gk[i_n:]), N.ptr(ck[i_n:]), N.ptr(gates), N.ptr(hf), N.ptr(h0f), N.ptr(dhs),
-                                     N.ptr(carry), N.ptr(dg), t_n, b_n, h_n, BF16, N.stream_ptr()), "gru_bwd")
-        x2, dg2 = x.view(t_n * b_n, i_n), dg.view(t_n * b_n, 3 * h_n)
-        dgate, dpc = dg2[:, :2 * h_n], dg2[:, 2 * h_n:]
-        dx = None
-        if ctx.needs_input_grad[0]:
-            wx = torch.cat([gk[:i_n], ck[:i_n]], 1)
-            dx = gemm._hand_dgrad(dg2, wx)
-            if dx is None:
-                dx = torch.mm(dg2, wx.t())
+        x2 = x.view(t_n * b_n, i_n)
+        rows, keep = [], []
+        for d in range(ndir):
+            gk, ck, h0b, h0f, hs, hf, rh, gates = saved[8 * d:8 * d + 8]
+            dhs = grads[2 * d].to(torch.bfloat16).contiguous()
+            carry = grads[2 * d + 1].float().clone()                    # dL/dh_T in, dL/dh_0 out
+            dg = torch.empty((t_n, b_n, 3 * h_n), dtype=torch.bfloat16, device=dev)
+            rows.append((gk[i_n:], ck[i_n:], gates, hf, h0f, dhs, carry, dg))
+            keep.append((dg.view(t_n * b_n, 3 * h_n), carry))
+        if ctx.plain:
+            N.check(N.fn("mdtf_gru_bwd")(*[N.ptr(z) for z in rows[0]], t_n, b_n, h_n, BF16, N.stream_ptr()), "gru_bwd")
+        else:
+            N.check(N.fn("mdtf_gru_bwd_seq")(rnn._table(rows), ndir, ctx.reverse, N.ptr(lens), t_n, b_n, h_n, BF16,
+                                             N.stream_ptr()), "gru_bwd_seq")
+        dx, out = None, []
+        for d in range(ndir):
+            gk, ck, h0b, _, hs, _, rh, _ = saved[8 * d:8 * d + 8]
+            like = ctx.like[5 * d:5 * d + 5]
+            dg2, carry = keep[d]
+            dgate, dpc = dg2[:, :2 * h_n], dg2[:, 2 * h_n:]
+            if ctx.needs_input_grad[0]:
+                wx = torch.cat([gk[:i_n], ck[:i_n]], 1)
+                if dx is None:
+                    dx = gemm._hand_dgrad(dg2, wx)
+                    if dx is None:
+                        dx = torch.mm(dg2, wx.t())
+                else:
+                    dx.addmm_(dg2, wx.t())                              # the second direction adds into the first's
+            grads_d = [None] * 4
+            if any(ctx.needs_input_grad[3 + 5 * d:7 + 5 * d]):
+                slots = [V.slot_or_zeros(s, p.shape, dev) for s, p in zip(ctx.sinks[d], like[:4])]
+                sgk, sgb, sck, scb = slots
+                if not gemm.wgrad_into(sgk[:i_n], x2, dgate, sgb):
+                    sgb.add_(torch.sum(dgate, 0, dtype=torch.float32))  # (a fixed-order sum: repeatable)
+                gemm.wgrad_into(sgk[i_n:], rnn._h_prev(h0b, hs, lens, (ctx.reverse >> d) & 1), dgate)
+                if not gemm.wgrad_into(sck[:i_n], x2, dpc, scb):
+                    scb.add_(torch.sum(dpc, 0, dtype=torch.float32))
+                gemm.wgrad_into(sck[i_n:], rh.view(t_n * b_n, h_n), dpc)
+                grads_d = [V.grad_marker(p) if s is not None else g.to(p.dtype)
+                           for s, g, p in zip(ctx.sinks[d], slots, like[:4])]
+            out += grads_d + [carry.to(like[4].dtype)]
+        if dx is not None:
             dx = dx.view(t_n, b_n, i_n)
-        grads = [None] * 4
-        if any(ctx.needs_input_grad[1:5]):
-            gk_like, gb_like, ck_like, cb_like = ctx.like[:4]
-            slots = [V.slot_or_zeros(s, p.shape, dev) for s, p in zip(ctx.sinks, ctx.like[:4])]
-            sgk, sgb, sck, scb = slots
-            h_prev = torch.cat([h0b[None], hs[:-1]], 0).view(t_n * b_n, h_n)
-            if not gemm.wgrad_into(sgk[:i_n], x2, dgate, sgb):
-                sgb.add_(torch.sum(dgate, 0, dtype=torch.float32))      # (a fixed-order sum: repeatable)
-            gemm.wgrad_into(sgk[i_n:], h_prev, dgate)
-            if not gemm.wgrad_into(sck[:i_n], x2, dpc, scb):
-                scb.add_(torch.sum(dpc, 0, dtype=torch.float32))
-            gemm.wgrad_into(sck[i_n:], rh.view(t_n * b_n, h_n), dpc)
-            grads = [V.grad_marker(p) if s is not None else g.to(p.dtype)
-                     for s, g, p in zip(ctx.sinks, slots, ctx.like[:4])]
-        return (dx,) + tuple(grads) + (carry.to(ctx.like[4].dtype),)
+        return (dx, None, None) + tuple(out)
 
 
 def _check_args(x, gk, gb, ck, cb, h0, sequence_length):
@@ -159,13 +214,33 @@ def _check_args(x, gk, gb, ck, cb, h0, sequence_length):
         raise ValueError("gru: sequence_length must have %d entries" % b_n)
 
 
-def gru(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length=None):
+def _cast(p, dtype):
+    """A direction's ``(gates_kernel, gates_bias, cand_kernel, cand_bias, h0)`` with both kernels in ``dtype``."""
+    return tuple(t.to(dtype) if j in (0, 2) and t.dtype != dtype else t for j, t in enumerate(p))
+
+
+def gru(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length=None, reverse=False):
     """``(hs, h_T)`` of the GRU over time-major ``x`` [T, B, I] from the state ``h0`` [B, H] (any dtype; its gradient
-    comes back in that dtype).  ``h_T`` is in the dtype of ``x`` and equals ``hs[-1]`` bit for bit on a full-length
-    call."""
-    _check_args(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length)
+    comes back in that dtype), in the ``reverse`` direction if asked.  ``h_T`` is in the dtype of ``x`` and has the
+    bits of ``hs`` at each row's last visited live step (``hs[-1]`` on a full-length forward call)."""
+    p = (gates_kernel, gates_bias, cand_kernel, cand_bias, h0)
+    _check_args(x, *p, sequence_length)
     if native_ok(x, cand_kernel, h0, sequence_length):
-        gk = gates_kernel if gates_kernel.dtype == x.dtype else gates_kernel.to(x.dtype)
-        ck = cand_kernel if cand_kernel.dtype == x.dtype else cand_kernel.to(x.dtype)
-        return _GRU.apply(x, gk, gates_bias, ck, cand_bias, h0)
-    return gru_loop(x, gates_kernel, gates_bias, cand_kernel, cand_bias, h0, sequence_length)
+        return _GRU.apply(x, rnn._device_lengths(sequence_length, x.device), int(bool(reverse)), *_cast(p, x.dtype))
+    return gru_loop(x, *p, sequence_length, reverse)
+
+
+def bigru(x, fw, bw, sequence_length=None):
+    """A forward-in-time and a reverse GRU over the same ``x`` [T, B, I] and lengths: ``((hs, h_T) of fw, the same of
+    bw)`` for ``fw`` / ``bw`` = ``(gates_kernel, gates_bias, cand_kernel, cand_bias, h0)``.  With the same ``H`` on the
+    kernel path every pair of step launches runs step s of ``fw`` and step ``T - 1 - s`` of ``bw``; otherwise the
+    directions run as two calls of :func:`gru`."""
+    for p in (fw, bw):
+        _check_args(x, *p, sequence_length)
+    if fw[2].shape == bw[2].shape and native_ok(x, fw[2], fw[4], sequence_length) and bw[4].is_cuda:
+        out = _GRU.apply(x, rnn._device_lengths(sequence_length, x.device), 0b10, *_cast(fw, x.dtype),
+                         *_cast(bw, x.dtype))
+        return out[:2], out[2:]
+    if sequence_length is not None and x.is_cuda:
+        sequence_length = rnn._device_lengths(sequence_length, x.device)    # copied once for both calls
+    return gru(x, *fw, sequence_length), gru(x, *bw, sequence_length, True)

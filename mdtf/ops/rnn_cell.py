@@ -5,10 +5,11 @@ A cell owns no tensors: ``dynamic_rnn`` creates ``<scope or "rnn">/lstm_cell/ker
 [4H] on first use -- TF's names and layout (gate order i, j, f, o; the input rows first), so a ``Saver`` bundle matches
 -- and runs the whole sequence through :func:`mdtf.ops.rnn.lstm`, ``sequence_length`` included; a ``GRUCell`` gets
 ``.../gru_cell/gates/{kernel,bias}`` [I + H, 2H] / [2H] (r then u) and ``.../gru_cell/candidate/{kernel,bias}``
-[I + H, H] / [H] and runs through :func:`mdtf.ops.gru.gru`.  ``bidirectional_dynamic_rnn`` runs LSTM cells under
-``<scope or "bidirectional_rnn">/fw`` and ``.../bw`` through :func:`mdtf.ops.rnn.bilstm`.  Peepholes, projection and
-cell clipping are not implemented; nor are vanilla cells, bidirectional GRUs, ``MultiRNNCell`` (stack layers by
-calling ``dynamic_rnn`` under different scopes) and dropout wrappers.
+[I + H, H] / [H] and runs through :func:`mdtf.ops.gru.gru`, ``sequence_length`` included.
+``bidirectional_dynamic_rnn`` runs LSTM cells under ``<scope or "bidirectional_rnn">/fw`` and ``.../bw`` through
+:func:`mdtf.ops.rnn.bilstm`; it refuses GRU cells, whose two-direction form is :func:`mdtf.ops.gru.bigru` /
+``mdtf.layers.tools.bigru``.  Peepholes, projection and cell clipping are not implemented; nor are vanilla cells,
+``MultiRNNCell`` (stack layers by calling ``dynamic_rnn`` under different scopes) and dropout wrappers.
 """
 import collections
 
@@ -134,7 +135,9 @@ def bidirectional_dynamic_rnn(cell_fw, cell_bw, inputs, sequence_length=None, in
                               initial_state_bw=None, dtype=None, time_major=False, scope=None):
     """``tf.nn.bidirectional_dynamic_rnn``: ``((out_fw, out_bw), (state_fw, state_bw))``.  ``cell_bw`` reads row b
     from ``sequence_length[b] - 1`` down to 0 and ``out_bw`` is in the time order of ``inputs``; past its length a row
-    is zero in both.  Variables: ``<scope or "bidirectional_rnn">/fw/lstm_cell/{kernel,bias}`` and ``.../bw/...``."""
+    is zero in both.  Variables: ``<scope or "bidirectional_rnn">/fw/lstm_cell/{kernel,bias}`` and ``.../bw/...``.
+    LSTM cells only: ``GRUCell``s raise ``TypeError`` here, and a forward plus a reverse GRU in the same launches is
+    :func:`mdtf.ops.gru.bigru` (``mdtf.layers.tools.bigru`` with TF's variable names)."""
     from . import rnn
     from ..train import variables as V
     for cell in (cell_fw, cell_bw):
