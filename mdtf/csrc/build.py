@@ -30,7 +30,7 @@ HIP_FLAGS = ["-O3", "-std=c++17", "--offload-arch=%s" % ARCH, "-fPIC", "-munsafe
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {"attention_causal.hip": _NO_PACKED_FP32, "attention_cross.hip": _NO_PACKED_FP32,
                    "conv_group.hip": _NO_PACKED_FP32, "lstm.hip": _NO_PACKED_FP32, "gru.hip": _NO_PACKED_FP32,
-                   "ctc.hip": _NO_PACKED_FP32}
+                   "ctc.hip": _NO_PACKED_FP32, "groupnorm.hip": _NO_PACKED_FP32}
 HOST_FLAGS = ["-O3", "-std=c++17", "-msse4.2", "-fPIC", "-pthread", "-Wall", "-Wno-unused-result"]
 
 

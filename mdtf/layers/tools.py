@@ -184,6 +184,17 @@ def batch_norm(x, legacy=False, training=True, decay=0.9, epsilon=1e-3, relu=Fal
     return ops.batch_norm(x, gamma, beta, mm, mv, training, decay, epsilon, relu, residual)
 
 
+def group_norm(x, groups=32, epsilon=1e-6, relu=False, name="GroupNorm"):
+    """``tf.contrib.layers.group_norm``: statistics per image over H, W and each of ``groups`` runs of adjacent
+    channels, with ``<name>/gamma`` (ones) and ``<name>/beta`` (zeros), TF contrib's variable names.
+    ``groups=C`` is instance normalization; ``groups=1`` is layer normalization over (H, W, C)."""
+    c = x.shape[-1]
+    with V.variable_scope(name, reuse=V.AUTO_REUSE if V.get_store().frozen else None):
+        gamma = V.get_variable('gamma', [c], initializer=V.constant_initializer(1.0), keep_fp32=True)
+        beta = V.get_variable('beta', [c], initializer=V.constant_initializer(0.0), keep_fp32=True)
+    return ops.group_norm(x, gamma, beta, groups, epsilon, "relu" if relu else None, name=name)
+
+
 def norm(name, x, lsize=4):
     """Local response normalisation; returns the LRN output (fix for SURVEY Q17)."""
     return ops.lrn(x, lsize, bias=1.0, alpha=0.001 / 9.0, beta=0.75, name=name)

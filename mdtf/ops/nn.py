@@ -357,6 +357,38 @@ def layer_norm(x, gamma, beta, epsilon=1e-12, residual=None):
     return transformer.layer_norm(x, gamma, beta, epsilon, residual)
 
 
+def group_norm(x, gamma, beta, groups=32, epsilon=1e-6, act=None, name=None, path=None):
+    """``tf.contrib.layers.group_norm`` of an NHWC ``x`` [N, H, W, C]: mean and biased variance per image over
+    H, W and each of the ``groups`` runs of ``C / groups`` adjacent channels, then ``gamma`` / ``beta`` [C] per
+    channel and ``act`` (None or ``"relu"``).  ``groups = C`` is instance normalization, ``groups = 1`` layer
+    normalization over (H, W, C).
+
+    bf16 GPU tensors with ``C % 8 == 0`` (and ``C <= 2048``) run the HIP kernels (``ops/groupnorm.py``; ``path``
+    picks their design: None auto, 1 resident, 2 streaming); CPU tensors, ``MDTF_KERNELS=torch``, fp32 activations
+    and other channel counts run the PyTorch expression: fp32 ``F.group_norm`` on the permuted tensor, then ``relu``,
+    returned in ``x``'s dtype and NHWC.
+    """
+    if x.dim() != 4:
+        raise ValueError("group_norm: x must be NHWC of rank 4, got rank %d" % x.dim())
+    c = x.shape[-1]
+    if groups < 1 or c % groups:
+        raise ValueError("group_norm: %d channels do not split into %d groups" % (c, groups))
+    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise ValueError("group_norm: gamma and beta must be [%d], got %s and %s" % (
+            c, tuple(gamma.shape), tuple(beta.shape)))
+    if act not in (None, "relu"):
+        raise ValueError("group_norm: act must be None or 'relu', got %r" % (act,))
+    from . import groupnorm
+    if groupnorm.native_ok(x, groups):
+        return groupnorm.group_norm_nhwc(x, gamma, beta, groups, epsilon, act == "relu", path)[0]
+    # a contiguous NCHW copy, not the permuted view: PyTorch's CPU backward of a channels-last input crashes when
+    # only the parameters need gradients (the first layer of a model)
+    y = F.group_norm(x.float().permute(0, 3, 1, 2).contiguous(), groups, gamma.float(), beta.float(), epsilon)
+    if act == "relu":
+        y = torch.relu(y)
+    return y.permute(0, 2, 3, 1).to(x.dtype)
+
+
 # ---------------------------------------------------------------------------
 # dense
 # ---------------------------------------------------------------------------
